@@ -15,11 +15,16 @@ the reference evaluates, graph/iterative_clustering.py:20-29) per scene × scene
 wall time; ms_per_step is the per-scene graph build + cluster time (BASELINE.json's first metric).
 Multi-GPU (--shard frames, default): one scene per step, its frames split over the ranks (strong
 scaling); --shard scene: every rank its own scene (weak scaling, run.py:33-50).
-At N=1 the line also carries `secondary`: the ScanNet-sized C2 scene (configs[1]) timed E2E and G
-in the same process, with the host ports beside it (c2_record).
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR also
+writes the last timed step's results (the scene's masks and every graph / clustering stage down to the
+objects' point sets) as DIR/<name>.npy; the inputs are the same from run to run (--seed).  --full adds
+what takes runs of its own: the calibration step with per-group event timing and the rooflines from
+it, the CPU baselines, the one-scene latency, and at N=1 `secondary`: the ScanNet-sized C2 scene
+(configs[1]) timed E2E and G in the same process, with the host ports beside it (c2_record).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--variant e2e|g|pp|api|sweep] [--shape S]
-                    [--no-cpu-baseline] [--no-secondary]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary] [--no-latency]]
 """
 from __future__ import annotations
 
@@ -536,6 +541,47 @@ class ShardedEndToEndStep(EndToEndStep):
                                 self.cfg)
 
 
+def step_outputs(runner):
+    """What a caller of the timed path holds after a step: the scene's masks (S1's output; the g
+    variant's input) and every graph and clustering stage down to the final objects' point sets, in
+    the order-free form of the golden fixtures (GraphRun.canonical without the dense P x F matrices)."""
+    run = runner.run
+    sh = getattr(runner, "sh", None)
+    if sh is not None:
+        col, lab, off = sh.mask_index
+        pts = sh.pts.cpu().numpy()
+    elif hasattr(runner, "scene"):
+        s = runner.scene
+        col, lab, off, pts = s.mask_col, s.mask_label, s.mask_off, s.mask_pts
+    else:
+        col, lab, off, pts = runner.ctx.bp_masks()
+    run.mask_col, run.mask_label = np.asarray(col, np.int32), np.asarray(lab, np.int32)
+    out = {"mask_col": col, "mask_label": lab, "mask_off": off, "mask_pts": pts}
+    out.update({k.lstrip("_"): v for k, v in run.canonical(dense=False).items()})
+    return out
+
+
+def dump_outputs(dirname, arrays, budget=60 << 20):
+    """arrays {name: array} as dirname/<name>.npy: float32 where every value is exact in it, else
+    float64; at most `budget` bytes in all.  An array beyond the per-array cap is written as a sample
+    of its flattened elements at fixed positions (seed 0, sorted), the same from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for k, v in arrays.items():
+        a = np.asarray(v)
+        small = a.dtype.kind == "b" or a.dtype == np.float32 or (
+            a.dtype.kind in "iu" and (a.size == 0 or max(abs(int(a.min())), abs(int(a.max()))) < 1 << 24))
+        conv[k] = (a, np.float32 if small else np.float64)
+    cap = 1 << 22
+    while sum(min(a.size, cap) * np.dtype(dt).itemsize for a, dt in conv.values()) > budget:
+        cap >>= 1
+    for k, (a, dt) in conv.items():
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, cap))]
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a, dtype=dt))
+    log(f"outputs: {len(conv)} arrays in {dirname} (cap {cap} elements per array)")
+
+
 def c2_record(local, steps, warmup):
     """The ScanNet-sized scene (BASELINE configs[1], the north_star's "ScanNet-sized scene on 1 MI355X")
     timed in the same process with the same discipline as the main line (warmup steps, then `steps`
@@ -789,7 +835,7 @@ def run_post_process(a):
            "filtered_objects": info.num_filtered, "final_objects": info.num_final,
            "output_points": int(sum(len(p) for p in pts)), "data": "synthetic"}
     budget = 15.0
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         from oracle import pp_oracle
         keys = list(mpc.keys())
         kidx = {k: i for i, k in enumerate(keys)}
@@ -911,9 +957,16 @@ def main():
                                                              "(default: also get_depth_raw, uint16 frames)")
     ap.add_argument("--shape", default=None, help="default: c3 (g, e2e), c2 (api, pp, sweep)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C2 E2E / G record (N=1 only)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the one-scene-at-a-time latency record")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the per-group calibration step and rooflines, the CPU "
+                         "baselines, the one-scene latency and the C2 secondary records (each takes runs of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="g, e2e: write the last timed step's results to DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB; arrays beyond their share as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C2 E2E / G record (N=1 only)")
+    ap.add_argument("--no-latency", action="store_true",
+                    help="--full: skip the one-scene-at-a-time latency record")
     ap.add_argument("--shard", choices=["scene", "frames"], default="frames",
                     help="frames: one scene, its frames split over the ranks, S2-S6 row-block sharded (strong "
                          "scaling; the north_star's ScanNet++-sized C3 by default); scene: every rank its own "
@@ -921,6 +974,10 @@ def main():
     args = ap.parse_args()
     if args.shape is None:
         args.shape = "c3" if args.variant in ("g", "e2e") else "c2"
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.variant not in ("g", "e2e"):
+        ap.error("--dump-outputs is for the g and e2e variants")
     if args.variant == "pp":
         return run_post_process(args)
     if args.variant == "api":
@@ -963,36 +1020,33 @@ def main():
     # (scene-owner mode: the warmup and calibration scenes are rank 0's, the other ranks hold no graph
     # result; they only time their share and join the max-reduce)
     has_graph = rank == 0 or not getattr(runner, "scene_owner", False)
-    pairs_per_step = 0
-    if has_graph:
-        ci = ctx.cluster_info()
-        sizes = ctx.level_sizes(ci.num_iterations)
-        pairs_per_step = int(np.sum(sizes[:-1].astype(np.int64) ** 2))
 
-    # calibration pass with per-group event timing: find the dominant kernel group
-    for c in tctxs:
-        c.reset_kernel_times()
-        c.set_timing(True)
-    runner.step()
-    for c in tctxs:
-        c.synchronize()
-    calib = {g: ktime(g) for g in runner.groups}
-    for c in tctxs:
-        c.set_timing(False)
-    work = runner.work() if has_graph else {}
-    for g in BP_GROUPS:  # S1 models are scene totals: per launch = total / the group's launches per scene
-        if g in work and calib.get(g, (0, 0))[1]:
-            b, tot, model, alt = work[g]
-            work[g] = (b, tot / calib[g][1], model + " per scene / launches per scene", alt)
-    dominant = max((g for g in calib if g in work), key=lambda g: calib[g][0]) if work else BP_GROUPS[0]
-    log("calibration (ms):", json.dumps({k: round(v[0], 4) for k, v in calib.items()}), "dominant:", dominant)
+    calib, work, dominant = {}, {}, None
+    if args.full:
+        # calibration pass with per-group event timing: find the dominant kernel group
+        for c in tctxs:
+            c.reset_kernel_times()
+            c.set_timing(True)
+        runner.step()
+        for c in tctxs:
+            c.synchronize()
+        calib = {g: ktime(g) for g in runner.groups}
+        for c in tctxs:
+            c.set_timing(False)
+        work = runner.work() if has_graph else {}
+        for g in BP_GROUPS:  # S1 models are scene totals: per launch = total / the group's launches per scene
+            if g in work and calib.get(g, (0, 0))[1]:
+                b, tot, model, alt = work[g]
+                work[g] = (b, tot / calib[g][1], model + " per scene / launches per scene", alt)
+        dominant = max((g for g in calib if g in work), key=lambda g: calib[g][0]) if work else BP_GROUPS[0]
+        log("calibration (ms):", json.dumps({k: round(v[0], 4) for k, v in calib.items()}), "dominant:", dominant)
 
-    # timed region: barrier + synchronize on both sides; live HIP-event timing of the dominant
-    # group only (one event pair per launch of the group, on the context stream)
-    for c in tctxs:
-        c.reset_kernel_times()
-        c.set_timing_filter(dominant)
-        c.set_timing(True)
+        # timed region: barrier + synchronize on both sides; live HIP-event timing of the dominant
+        # group only (one event pair per launch of the group, on the context stream)
+        for c in tctxs:
+            c.reset_kernel_times()
+            c.set_timing_filter(dominant)
+            c.set_timing(True)
     pipe = getattr(runner, "pipe", None)
     if pipe is not None:
         pipe.gather_s, pipe.gathers = 0.0, 0
@@ -1011,12 +1065,19 @@ def main():
     elapsed = time.perf_counter() - t0
     for c in tctxs:
         c.set_timing(False)
-    dom_ms, dom_n = ktime(dominant)
+    dom_ms, dom_n = ktime(dominant) if args.full else (0.0, 0)
     gather_ms = 1e3 * pipe.gather_s / max(pipe.gathers, 1) if pipe is not None else 0.0
+    pairs_per_step = 0
+    if has_graph:  # the last timed step's result
+        ci = ctx.cluster_info()
+        sizes = ctx.level_sizes(ci.num_iterations)
+        pairs_per_step = int(np.sum(sizes[:-1].astype(np.int64) ** 2))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step_outputs(runner))
     # the one-scene-at-a-time latency beside the pipelined throughput (frame-sharded e2e with the pipeline):
     # the same barrier / synchronize discipline, max over ranks
     lat_elapsed, lat_n = 0.0, 0
-    if pipe is not None and hasattr(runner, "latency_steps") and not args.no_latency:
+    if args.full and pipe is not None and hasattr(runner, "latency_steps") and not args.no_latency:
         lat_n = max(2, min(args.steps, 5))
         runner.latency_steps(1)  # its graph context's first call
         torch.cuda.synchronize()
@@ -1044,6 +1105,35 @@ def main():
     total_pairs = pairs_per_step * args.steps * (1 if frames else world)
     value = total_pairs / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    line = {
+        "metric": "mask-pair consensus counts/sec (per-scene graph build+cluster)",
+        "value": round(value, 1),
+        "unit": "mask-pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if frames else "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic",
+        "config": {"workload": runner.workload + f" M={gi.num_masks}", "variant": args.variant,
+                   "dataset_config": f"configs/{runner.dataset}.json", "thresholds": runner.cfg,
+                   "scene_ms": round(ms_per_step, 4), "pairs_per_scene": pairs_per_step,
+                   "iterations": int(ci.num_iterations), "objects": int(ci.num_objects),
+                   "parallelism": (f"frame-sharded x{world}" + (", scene-owner graph stages"
+                                                                 if getattr(runner, "scene_owner", False) else "")
+                                   if frames else f"scene-parallel x{world}"),
+                   "scene_pipeline": getattr(runner, "pipe", None) is not None,
+                   "s1_producers": len(runner.pipe.s1s) if getattr(runner, "pipe", None) is not None else 0},
+    }
+    if not args.full:  # the plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # HBM bytes per launch of every kernel group from the committed rocprofv3 PMC passes of the
     # same workload (scripts/pmc_summary.py; FETCH_SIZE doubled per the gfx950 note in
@@ -1149,29 +1239,8 @@ def main():
                                       "filter, overlap merge; host packing included) on the c2_api run's objects"}
 
     if rank == 0:
-        line = {
-            "metric": "mask-pair consensus counts/sec (per-scene graph build+cluster)",
-            "value": round(value, 1),
-            "unit": "mask-pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if frames else "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic",
-            "config": {"workload": runner.workload + f" M={gi.num_masks}", "variant": args.variant,
-                       "dataset_config": f"configs/{runner.dataset}.json", "thresholds": runner.cfg,
-                       "scene_ms": round(ms_per_step, 4), "pairs_per_scene": pairs_per_step,
-                       "iterations": int(ci.num_iterations), "objects": int(ci.num_objects),
-                       "stage_ms": {k: round(v[0], 4) for k, v in calib.items()},
-                       "parallelism": (f"frame-sharded x{world}" + (", scene-owner graph stages"
-                                                                     if getattr(runner, "scene_owner", False) else "")
-                                       if frames else f"scene-parallel x{world}"),
-                       "scene_pipeline": getattr(runner, "pipe", None) is not None,
-                       "s1_producers": len(runner.pipe.s1s) if getattr(runner, "pipe", None) is not None else 0},
+        line["config"]["stage_ms"] = {k: round(v[0], 4) for k, v in calib.items()}
+        line.update({
             # SURVEY.md §8(d)'s own definition of the pair metric: the same pairs over S6's time only
             "pairs_per_s_s6": round(pairs_per_step / max(s6_ms / 1e3, 1e-12), 1),
             "pairs_per_s_s6_def": "sum_t N_t^2 / sum_t (S6 iteration t's device time: s6_columns + s6_pairs + "
@@ -1179,7 +1248,7 @@ def main():
             "roofline": roof,
             "stage_roofline": stages,
             "cpu_baseline": cpu,
-        }
+        })
         if world > 1:
             line["rccl_comm_ranks"] = rccl_ranks  # ncclCommCount on the job's communicator (None under gloo)
             line["backend"] = dist.get_backend()

@@ -142,18 +142,36 @@ def make_frames(num_objects, num_frames, H, W, length, spacing, size, seed=0, p_
     vv, uu = torch.meshgrid(v, u, indexing="ij")
     dirs_cam = torch.stack([(uu - ccx) / fx, (vv - ccy) / fy, torch.ones_like(uu)], dim=-1).reshape(-1, 3)
     ucol = torch.arange(W, device=dev)[None, :]
+    # the eight corners of every box, for its screen bounds in each frame
+    corners = np.stack([np.where(np.array([i0, i1, i2], bool), bmax, bmin)
+                        for i0 in (0, 1) for i1 in (0, 1) for i2 in (0, 1)], axis=1)  # [K, 8, 3]
+    strip_w = 240
     if out == "torch":
         depth = torch.zeros((len(sel), H, W), dtype=torch.float32, device=dev)
         seg = torch.zeros((len(sel), H, W), dtype=torch.uint8, device=dev)
     else:
         depth = np.zeros((len(sel), H, W), np.float32)
         seg = np.zeros((len(sel), H, W), np.uint8)
-    chunk = 32 if H * W <= 400_000 else 8
     for i, f in enumerate(sel):
         R = torch.tensor(poses[f, :3, :3], dtype=torch.float64, device=dev)
         c = torch.tensor(poses[f, :3, 3], dtype=torch.float64, device=dev)
         d = dirs_cam @ R.T                       # world direction per unit camera depth
         near = np.nonzero(np.abs(cx - poses[f, 0, 3]) < 4.5)[0]
+        # a ray can meet a box only inside the bounding rectangle of the box's projected corners (2 pixels
+        # of slack for rounding; a box that reaches behind the camera counts as the whole screen): boxes
+        # off the screen are dropped, the others are tested against the rays of their columns and rows only
+        cam = (corners[near] - poses[f, :3, 3]) @ poses[f, :3, :3]
+        front = cam[..., 2].min(axis=1) > 0.1
+        zc = np.where(front[:, None], cam[..., 2], 1.0)
+        pu, pv = fx * cam[..., 0] / zc + ccx, fy * cam[..., 1] / zc + ccy
+        u0 = np.where(front, np.floor(pu.min(axis=1)) - 2, 0)
+        u1 = np.where(front, np.ceil(pu.max(axis=1)) + 2, W - 1)
+        v0 = np.where(front, np.floor(pv.min(axis=1)) - 2, 0)
+        v1 = np.where(front, np.ceil(pv.max(axis=1)) + 2, H - 1)
+        on = (u1 >= 0) & (u0 <= W - 1) & (v1 >= 0) & (v0 <= H - 1)
+        near = near[on]
+        u0, u1 = np.clip(u0[on], 0, W - 1).astype(np.int64), np.clip(u1[on], 0, W - 1).astype(np.int64)
+        v0, v1 = np.clip(v0[on], 0, H - 1).astype(np.int64), np.clip(v1[on], 0, H - 1).astype(np.int64)
         best_t = torch.full((H * W,), float("inf"), dtype=torch.float64, device=dev)
         best_o = torch.full((H * W,), -1, dtype=torch.int64, device=dev)
         # floor (z = 0) and back wall (y = 3.2): depth without a mask
@@ -162,18 +180,28 @@ def make_frames(num_objects, num_frames, H, W, length, spacing, size, seed=0, p_
             tw = torch.where(d[:, 1] > 1e-9, (3.2 - c[1]) / d[:, 1], torch.full_like(best_t, float("inf")))
             bg = torch.minimum(tf, tw)
             inv = 1.0 / torch.where(d.abs() < 1e-12, torch.full_like(d, 1e-12), d)
-            for k0 in range(0, len(near), chunk):
-                idx = torch.as_tensor(near[k0:k0 + chunk], device=dev)
-                t0 = (tb0[idx][None] - c) * inv[:, None]     # [R, B, 3]
-                t1 = (tb1[idx][None] - c) * inv[:, None]
-                tn = torch.minimum(t0, t1).amax(-1)
-                tx = torch.maximum(t0, t1).amin(-1)
-                hit = (tn <= tx) & (tn > 0.05)
-                tn = torch.where(hit, tn, torch.full_like(tn, float("inf")))
-                tmin, arg = tn.min(-1)
-                better = tmin < best_t
-                best_t = torch.where(better, tmin, best_t)
-                best_o = torch.where(better, idx[arg], best_o)
+            bt2, bo2, inv3 = best_t.view(H, W), best_o.view(H, W), inv.view(H, W, 3)
+            for a in range(0, W, strip_w):
+                b = min(a + strip_w, W)
+                s = np.nonzero((u0 < b) & (u1 >= a))[0]
+                if not len(s):
+                    continue
+                r0, r1 = int(v0[s].min()), int(v1[s].max()) + 1
+                inv_t = inv3[r0:r1, a:b, None, :]
+                chunk = max(8, min(32, 6_000_000 // ((r1 - r0) * (b - a))))
+                for k0 in range(0, len(s), chunk):
+                    idx = torch.as_tensor(near[s[k0:k0 + chunk]], device=dev)
+                    t0 = (tb0[idx] - c) * inv_t              # [rows, cols, B, 3]
+                    t1 = (tb1[idx] - c) * inv_t
+                    tn = torch.minimum(t0, t1).amax(-1)
+                    tx = torch.maximum(t0, t1).amin(-1)
+                    hit = (tn <= tx) & (tn > 0.05)
+                    tn = torch.where(hit, tn, torch.full_like(tn, float("inf")))
+                    tmin, arg = tn.min(-1)
+                    cur_t, cur_o = bt2[r0:r1, a:b], bo2[r0:r1, a:b]
+                    better = tmin < cur_t
+                    bt2[r0:r1, a:b] = torch.where(better, tmin, cur_t)
+                    bo2[r0:r1, a:b] = torch.where(better, idx[arg], cur_o)
             use_obj = best_t < bg
             t = torch.where(use_obj, best_t, bg).reshape(H, W)
             obj = torch.where(use_obj, best_o, torch.full_like(best_o, -1)).reshape(H, W)

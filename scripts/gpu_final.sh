@@ -19,9 +19,9 @@ if [ "$PART" = records ]; then
   run timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
       || { tail -20 "$OUT/smoke.log"; exit 1; }
   tail -1 "$OUT/smoke.log"
-  run timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+  run timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
   cat "$OUT/bench.json"
-  run timeout -k 10 300 python bench.py --shape c4 --steps 5 --warmup 1 --no-cpu-baseline --no-secondary \
+  run timeout -k 10 300 python bench.py --full --shape c4 --steps 5 --warmup 1 --no-cpu-baseline --no-secondary \
       > "$OUT/bench_e2e_c4.json" 2> "$OUT/bench_e2e_c4.err" || { tail -20 "$OUT/bench_e2e_c4.err"; exit 1; }
   run timeout -k 10 300 python bench.py --variant sweep > "$OUT/bench_sweep_c5.json" 2> "$OUT/bench_sweep_c5.err" \
       || { tail -20 "$OUT/bench_sweep_c5.err"; exit 1; }
@@ -54,7 +54,7 @@ done
 python3 scripts/pmc_kernel.py "k_bp_" "$RAW"/sq*.csv > "$OUT/denoise_sq_counters_c3.json"
 rm -rf "$RAW"
 run timeout -k 10 300 env MC_BENCH_DEVICE=0 MC_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus 2 --steps 4 --warmup 1 \
+    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 bench.py --full --gpus 2 --steps 4 --warmup 1 \
     > "$OUT/n2_e2e_c3.json" 2> "$OUT/n2_e2e_c3.err" || { tail -20 "$OUT/n2_e2e_c3.err"; exit 1; }
 run timeout -k 10 400 python scripts/rank_proxy.py c3 6 2 4 8 > "$OUT/rank_proxy_c3.jsonl" 2> "$OUT/rank_proxy_c3.err" \
     || { tail -20 "$OUT/rank_proxy_c3.err"; exit 1; }

@@ -19,7 +19,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
       || { tail -20 "$OUT/smoke.log"; exit 1; }
   tail -2 "$OUT/smoke.log"
 fi
-run timeout -k 10 600 python bench.py --steps "$STEPS" --warmup 3 $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" \
+run timeout -k 10 600 python bench.py --full --steps "$STEPS" --warmup 3 $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" \
     || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 [ "${SKIP_PROF:-0}" = 1 ] && exit 0
