@@ -313,6 +313,53 @@ int mc_pp_get_info(mc_ctx *ctx, mc_pp_info *info);
 int mc_pp_get_results(mc_ctx *ctx, int32_t *entry_object, int32_t *mask_object, double *mask_coverage,
                       uint8_t *object_state, int32_t *object_node, double *object_bbox);
 
+/* mc_pp_run with every array a device pointer (same arguments and layouts).  The checks and the
+ * per-node layout run as kernels behind one flag the host reads once: a node mask whose frame is
+ * not visible to its node still fails with MC_ERR_INVALID, a node spanning more than 2^21 DBSCAN
+ * cells with MC_ERR_UNSUPPORTED.  Inside the call only O(num_nodes + num_objects) words cross
+ * between host and device (node offsets and the size order, per-object counts and boxes);
+ * nothing proportional to points, mask points or P x F does.  The per-entry results stay on the
+ * device; mc_pp_get_info / mc_pp_get_results work as after mc_pp_run (the getter fetches them). */
+int mc_pp_run_device(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points, int32_t num_frames,
+                     const double *scene_xyz, const uint64_t *pfm_bits, int32_t num_masks, const int64_t *mask_off,
+                     const int32_t *mask_pts, int32_t num_nodes, const uint64_t *node_vf_bits,
+                     const int64_t *node_pt_off, const int32_t *node_pts, const int64_t *node_mask_off,
+                     const int32_t *node_masks, const int32_t *node_mask_col);
+/* The same on the context's own S1-S6 result (after mc_cluster_run on a graph built from
+ * mc_scene_set_masks), nothing downloaded.  Nodes: the clustered objects with at least 2 level-0
+ * masks (post_process.py:182) in object-id order; a node's points: the object's, in the order
+ * mc_cluster_get_objects returns them (ascending); its masks: its level-0 members in ascending
+ * level-0 node id, each as its row of the mc_scene_set_masks input (which is the mask table of
+ * this run) with its frame column; its visible frames: the object's.  This is the canonical-order
+ * result: contents follow the reference's algorithm on these orders, not on the reference
+ * process's set orders.  scene_xyz: P x 3 float64 on the host or the device,
+ * or NULL for the float32 points of mc_scene_set_points widened exactly.  (When the input held
+ * masks of frames without points, which the context's table skips, the kept rows' input indices
+ * are uploaded: num_masks words.)
+ * MC_ERR_STATE: before mc_cluster_run; NULL scene_xyz without points set; nodes given by
+ * mc_nodes_set; a sharded context whose exchange is still pending on this rank. */
+int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *scene_xyz, int scene_on_device);
+
+/* ---- export of the final objects (utils/post_process.py:126-128, 148-165) ---------------------
+ * After any of the three mc_pp_run* calls.  Objects are the final ones in DBSCAN-object order
+ * (the reference's total_*_list order after the merge).  mc_pp_export_info gives the sizes;
+ * mc_pp_export fills the arrays (any pointer may be NULL), host pointers or, with on_device,
+ * device pointers:
+ *   obj_pt_off [num_final+1], obj_pts     kept points of each object, in its node's point order
+ *   obj_mask_off [num_final+1], obj_masks, obj_mask_cov
+ *                                         the masks assigned to it, in its node's mask_list order,
+ *                                         as mask-table rows, and their coverages
+ *   obj_repre [num_final*5]               find_represent_mask: positions into the object's mask
+ *                                         list of its five largest coverages (equal coverages in
+ *                                         list order, like Python's stable sort), padded with -1
+ *   obj_node [num_final]                  the node each object came from
+ * mc_pp_export_pred_masks fills the [num_points, num_final] uint8 row-major matrix the
+ * reference's prediction npz stores (what mc_eval_match_counts reads). */
+int mc_pp_export_info(mc_ctx *ctx, int32_t *num_final, int64_t *num_points, int64_t *num_masks);
+int mc_pp_export(mc_ctx *ctx, int64_t *obj_pt_off, int32_t *obj_pts, int64_t *obj_mask_off, int32_t *obj_masks,
+                 double *obj_mask_cov, int32_t *obj_repre, int32_t *obj_node, int on_device);
+int mc_pp_export_pred_masks(mc_ctx *ctx, uint8_t *out /* num_points*num_final */, int on_device);
+
 /* ---- instance-evaluation match counts -------------------------------
  * Replaces the device part of evaluation/evaluate.py:254-329 (assign_instances_for_scan): per
  * predicted mask k (column k of the [P, K] pred_masks matrix of the prediction npz, non-zero =

@@ -36,7 +36,8 @@ EXPORTED = [
     "mc_backproject_get_info", "mc_backproject_get_batching",
     "mc_backproject_get_masks", "mc_backproject_get_candidates", "mc_scene_use_backprojection",
     "mc_backproject_copy_points_device",
-    "mc_pp_run", "mc_pp_get_info", "mc_pp_get_results", "mc_eval_match_counts", "mc_frames_decode",
+    "mc_pp_run", "mc_pp_get_info", "mc_pp_get_results", "mc_pp_run_device", "mc_pp_run_clustered",
+    "mc_pp_export_info", "mc_pp_export", "mc_pp_export_pred_masks", "mc_eval_match_counts", "mc_frames_decode",
     "mc_shard_set", "mc_shard_pending", "mc_shard_export", "mc_shard_import",
     "mc_cluster_set_edge_capture", "mc_cluster_get_edges", "mc_openvoc_query", "mc_bits_unpack", "mc_setorder_replay",
     "mc_setorder_begin", "mc_setorder_finish", "mc_setorder_free",
@@ -173,6 +174,11 @@ def load():
         "mc_pp_run": (ctypes.c_int, [vp, P(PPParams), i64, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "mc_pp_get_info": (ctypes.c_int, [vp, P(PPInfo)]),
         "mc_pp_get_results": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+        "mc_pp_run_device": (ctypes.c_int, [vp, P(PPParams), i64, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "mc_pp_run_clustered": (ctypes.c_int, [vp, P(PPParams), vp, ctypes.c_int]),
+        "mc_pp_export_info": (ctypes.c_int, [vp, P(i32), P(i64), P(i64)]),
+        "mc_pp_export": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int]),
+        "mc_pp_export_pred_masks": (ctypes.c_int, [vp, vp, ctypes.c_int]),
         "mc_eval_match_counts": (ctypes.c_int, [vp, i64, i32, vp, vp, i32, vp, vp, vp, vp]),
         "mc_frames_decode": (ctypes.c_int, [vp, i32, i32, i32, vp, dbl, i32, i32, vp, ctypes.c_int, vp, vp]),
         "mc_shard_set": (ctypes.c_int, [vp, i32, i32]),
@@ -695,6 +701,7 @@ def _pp_methods():
                  vf=np.ascontiguousarray(node_vf_bits, np.uint64), poff=np.ascontiguousarray(node_pt_off, np.int64),
                  pts=np.ascontiguousarray(node_pts, np.int32), qoff=np.ascontiguousarray(node_mask_off, np.int64),
                  qm=np.ascontiguousarray(node_masks, np.int32), qc=np.ascontiguousarray(node_mask_col, np.int32))
+        self._pp_points = a["scene"].shape[0]
         self._check(self.L.mc_pp_run(self.h, ctypes.byref(params), a["scene"].shape[0], int(num_frames), _ptr(a["scene"]),
                                      _ptr(a["pfm"]), len(a["moff"]) - 1, _ptr(a["moff"]), _ptr(a["mpts"]),
                                      len(a["poff"]) - 1, _ptr(a["vf"]), _ptr(a["poff"]), _ptr(a["pts"]), _ptr(a["qoff"]),
@@ -717,7 +724,88 @@ def _pp_methods():
         n = dict(entry_object=E, mask_object=Q, mask_coverage=Q, object_state=K, object_node=K, object_bbox=K)
         return {k: v[:n[k]] for k, v in r.items()}
 
-    for f in (pp_run, pp_info, pp_results):
+    def _dptr(t):
+        return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+
+    def pp_run_device(self, params: PPParams, scene_xyz, pfm_bits, num_frames, mask_off, mask_pts, node_vf_bits,
+                      node_pt_off, node_pts, node_mask_off, node_masks, node_mask_col):
+        """mc_pp_run_device: the arguments of pp_run as contiguous device tensors (scene f64 [P,3], bit
+        rows as int64/uint64 words, offsets int64, indices int32)."""
+        import torch
+        want = dict(scene=torch.float64, moff=torch.int64, mpts=torch.int32, poff=torch.int64, pts=torch.int32,
+                    qoff=torch.int64, qm=torch.int32, qc=torch.int32)
+        a = dict(scene=scene_xyz, pfm=pfm_bits, moff=mask_off, mpts=mask_pts, vf=node_vf_bits, poff=node_pt_off,
+                 pts=node_pts, qoff=node_mask_off, qm=node_masks, qc=node_mask_col)
+        for k, t in a.items():
+            if t.device.type != "cuda" or not t.is_contiguous() or (k in want and t.dtype != want[k]) or \
+                    (k in ("pfm", "vf") and t.element_size() != 8):
+                raise ValueError(f"pp_run_device: {k} must be a contiguous device tensor of the documented type")
+        off = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731  (offsets hold at least one entry)
+        self._pp_points = a["scene"].shape[0]
+        self._check(self.L.mc_pp_run_device(self.h, ctypes.byref(params), a["scene"].shape[0], int(num_frames),
+                                            _dptr(a["scene"]), _dptr(a["pfm"]), len(a["moff"]) - 1, off(a["moff"]),
+                                            _dptr(a["mpts"]), len(a["poff"]) - 1, _dptr(a["vf"]), off(a["poff"]),
+                                            _dptr(a["pts"]), off(a["qoff"]), _dptr(a["qm"]), _dptr(a["qc"])))
+
+    def pp_run_clustered(self, params: PPParams, scene_xyz=None):
+        """mc_pp_run_clustered on the context's S1-S6 result.  scene_xyz: None (the float32 points of
+        set_points, widened), a float64 [P,3] numpy array, or a contiguous float64 device tensor."""
+        if scene_xyz is None:
+            ptr, dev, keep = None, 0, None
+        elif hasattr(scene_xyz, "data_ptr"):
+            import torch
+            if scene_xyz.device.type != "cuda" or scene_xyz.dtype != torch.float64 or not scene_xyz.is_contiguous():
+                raise ValueError("pp_run_clustered: a device scene must be a contiguous float64 tensor")
+            ptr, dev, keep = ctypes.c_void_p(scene_xyz.data_ptr()), 1, scene_xyz
+        else:
+            keep = np.ascontiguousarray(scene_xyz, np.float64)
+            ptr, dev = _ptr(keep), 0
+        self._check(self.L.mc_pp_run_clustered(self.h, ctypes.byref(params), ptr, dev))
+        self._pp_points = int(self.graph_info().num_points)
+
+    def pp_export_sizes(self):
+        nf, npt, nm = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.L.mc_pp_export_info(self.h, ctypes.byref(nf), ctypes.byref(npt), ctypes.byref(nm)))
+        return nf.value, npt.value, nm.value
+
+    def pp_export(self, device: bool = False):
+        """mc_pp_export: dict of obj_pt_off, obj_pts, obj_mask_off, obj_masks, obj_mask_cov, obj_repre
+        [num_final, 5] and obj_node: numpy arrays, or tensors on the context's device."""
+        nf, npt, nm = self.pp_export_sizes()
+        shapes = dict(obj_pt_off=(nf + 1, "int64"), obj_pts=(npt, "int32"), obj_mask_off=(nf + 1, "int64"),
+                      obj_masks=(nm, "int32"), obj_mask_cov=(nm, "float64"), obj_repre=(nf * 5, "int32"),
+                      obj_node=(nf, "int32"))
+        if device:
+            import torch
+            r = {k: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=self.torch_device)
+                 for k, (n, dt) in shapes.items()}
+            p = [ctypes.c_void_p(r[k].data_ptr()) for k in shapes]
+        else:
+            r = {k: np.zeros(max(n, 1), dt) for k, (n, dt) in shapes.items()}
+            p = [_ptr(r[k]) for k in shapes]
+        self._check(self.L.mc_pp_export(self.h, *p, 1 if device else 0))
+        r = {k: v[:shapes[k][0]] for k, v in r.items()}
+        r["obj_repre"] = r["obj_repre"].reshape(nf, 5)
+        return r
+
+    def pp_pred_masks(self, num_points: int | None = None, device: bool = False):
+        """mc_pp_export_pred_masks: the [P, num_final] uint8 matrix of the prediction npz (P: the
+        scene of the last pp_run* call of this object when not given)."""
+        nf = self.pp_export_sizes()[0]
+        if num_points is None:
+            num_points = self._pp_points
+        n = int(num_points) * nf
+        if device:
+            import torch
+            out = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.torch_device)
+            p = ctypes.c_void_p(out.data_ptr())
+        else:
+            out = np.zeros(max(n, 1), np.uint8)
+            p = _ptr(out)
+        self._check(self.L.mc_pp_export_pred_masks(self.h, p, 1 if device else 0))
+        return out[:n].reshape(int(num_points), nf)
+
+    for f in (pp_run, pp_info, pp_results, pp_run_device, pp_run_clustered, pp_export_sizes, pp_export, pp_pred_masks):
         setattr(Context, f.__name__, f)
 
 

@@ -32,10 +32,14 @@ class SceneSweep:
         self.cfg = dict(thresholds)
         self.prm = params if params is not None else _native.bp_params()
 
-    def run_scene(self, points, depth, seg, intrinsics, poses) -> int:
+    def run_scene(self, points, depth, seg, intrinsics, poses, post_process=None) -> int:
         """points float32 [P,3], depth f32 [F,H,W], seg u8 [F,H,W], intrinsics f64 [F,4], poses f64
         [F,16]: contiguous torch tensors on the device.  Returns the scene's object count; the
-        context holds the scene's full result (GraphRun.canonical, the getters)."""
+        context holds the scene's full result (GraphRun.canonical, the getters).
+
+        post_process: a ``PPParams``: the clustered objects are post-processed on the device as well
+        (``mc_pp_run_clustered`` on the scene's float32 points) and the count of final objects is
+        returned; ``objects()`` and ``pred_masks()`` give the reference's final product."""
         for t in (points, depth, seg, intrinsics, poses):
             if t.device.type != "cuda" or not t.is_contiguous():
                 raise ValueError("scene inputs must be contiguous device tensors")
@@ -48,4 +52,17 @@ class SceneSweep:
         self.run.mask_col, self.run.mask_label = np.asarray(col), np.asarray(lab)
         self.ctx.use_backprojection()
         self.run.step(**self.cfg)
-        return int(self.ctx.cluster_info().num_objects)
+        if post_process is None:
+            return int(self.ctx.cluster_info().num_objects)
+        self.ctx.pp_run_clustered(post_process)
+        return int(self.ctx.pp_info().num_final)
+
+    def objects(self, device: bool = False) -> dict:
+        """The final objects of the last ``run_scene(..., post_process=...)`` (``Context.pp_export``):
+        per-object point lists, mask lists (rows of the scene's mask table: ``run.mask_col`` /
+        ``run.mask_label``) with coverages, representative masks and source nodes."""
+        return self.ctx.pp_export(device=device)
+
+    def pred_masks(self, device: bool = False):
+        """The [P, num_final] uint8 matrix of the reference's prediction npz."""
+        return self.ctx.pp_pred_masks(self.run.P, device=device)

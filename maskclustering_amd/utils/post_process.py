@@ -210,6 +210,27 @@ def _post_process_objects(node_list, mask_point_clouds, scene_points, point_fram
     return out_pts, out_masks
 
 
+def post_process_device(run, frame_list, point_filter_threshold, scene_points=None, dbscan_eps=0.1,
+                        dbscan_min_points=4, overlapping_ratio=0.8):
+    """post_process.py:180-194 on a clustered ``GraphRun`` without leaving the device
+    (``mc_pp_run_clustered`` + ``mc_pp_export``): returns (total_point_ids_list, total_mask_list) as
+    ``export`` takes them.  The canonical-order result: a node's points ascending, its masks in
+    ascending level-0 node id; the reference's own set orders stay with
+    ``post_process``.  scene_points None: the float32 points of ``set_points``, widened."""
+    prm = PPParams(float(dbscan_eps), int(dbscan_min_points), float(point_filter_threshold), float(overlapping_ratio))
+    run.ctx.pp_run_clustered(prm, scene_points)
+    r = run.ctx.pp_export()
+    po, mo = r["obj_pt_off"].tolist(), r["obj_mask_off"].tolist()
+    pts = r["obj_pts"].astype(np.int64)
+    rows = r["obj_masks"]
+    fids = np.asarray(frame_list)[np.asarray(run.mask_col)[rows]].tolist()
+    labs = np.asarray(run.mask_label)[rows].tolist()
+    cov = r["obj_mask_cov"].tolist()
+    out_pts = [pts[a:b] for a, b in zip(po[:-1], po[1:])]
+    out_masks = [list(zip(fids[a:b], labs[a:b], cov[a:b])) for a, b in zip(mo[:-1], mo[1:])]
+    return out_pts, out_masks
+
+
 def find_represent_mask(mask_info_list):
     """post_process.py:126-128: the five masks of largest coverage (sorts the list in place)."""
     mask_info_list.sort(key=lambda x: x[2], reverse=True)
