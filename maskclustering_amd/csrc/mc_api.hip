@@ -9,9 +9,11 @@
 #include <limits>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "mc_internal.hpp"
+#include "mc_bp_plan.hpp"
 #include "mc_kernels.inl"
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
@@ -47,6 +49,63 @@ enum Stat : int {
 // kernels (k6_compress .. k6_memscatter, five launches)
 constexpr int kFusedComponentsMaxN0 = 32768;
 
+// MC_STAGE_THREADS: host threads of the staging copies (mc_backproject_frames, mc_bits_unpack)
+int stage_threads_knob(int dflt)
+{
+    if (const char *e = getenv("MC_STAGE_THREADS")) return std::max(1, std::min(64, atoi(e)));
+    return dflt;
+}
+
+// S1 back-projection state of a context (the host code is mc_bp_host.inl)
+struct BpState {
+    // scene points and their 2r grid
+    int64_t P = 0;
+    bool have_points = false, have_result = false;
+    float grid_radius = -1.f;  // scene grid built for this ball radius
+    unsigned gnb = 0;
+    DevBuf scene, gcnt, gstart, gbkt, gcellk, gpts, gidx, gcell, gscan_tmp;
+    // frames that arrive from the host
+    DevBuf in_depth, in_seg, in_intr, in_pose, in_raw;
+    char *h_stage[2] = {nullptr, nullptr};  // pinned staging ring of mc_backproject_frames (two chunks, ping-pong)
+    size_t stage_bytes = 0;
+    hipEvent_t ev_stage[2] = {};
+    bool stage_used[2] = {false, false};
+    hipStream_t copy = nullptr;  // host frames staged batch by batch while the previous batch computes
+    hipEvent_t ev_up = nullptr;
+    // per-batch arrays
+    DevBuf band, present, fflags, cand, npix, csidx, poff, slot_of, stat;
+    DevBuf vid;  // valid-id map (k_bp_count -> k_bp_compact), 1 byte per pixel
+    DevBuf slot_frame, slot_id, slot_np, slot_pix, slot_nv, slot_m, slot_ns, slot_box, slot_nn, slot_toff, slot_cov;
+    DevBuf pix_list, hkey, hvid, hfirst, vox_entry, acc, vpts, pcell, pbkt, bcnt, bstart, blist, ncnt, par, droot, rnk,
+        lab, ccnt, ssidx, avg, qpts;
+    DevBuf bm, tmp, kflag, ksize, midx, moff, out_col, out_label, out_off;
+    DevBuf cls_list, nbl, lean, vox_order;  // denoise size-class slot lists; per-workgroup eps-neighbour lists, lean scratch
+    DevBuf vx_pvid, vx_list, vx_fb;  // voxel_down_sample: per-pixel voxel ids and voxel lists of k_bp_voxel_lds; its overflow slots
+    DevBuf scanm;      // block sums of the multi-workgroup scans
+    DevBuf slot_grid;  // denoise: grid origin / extent of the slots with points queued for the k-NN ring search
+    DevBuf pack;       // the batch's readback, packed (k_bp_pack)
+    int *h_pack = nullptr;  // its pinned copy, h_pack_n ints
+    size_t h_pack_n = 0;
+    hipEvent_t ev_pack = nullptr;  // the last batch's h_pack copy (appended under the next batch)
+    int *h_stat = nullptr;         // pinned copy of the status block
+    hipStream_t cls_stream[mc::kBpStreamClasses] = {};  // denoise: the LDS size classes run side by side
+    hipEvent_t ev_cls[mc::kBpStreamClasses] = {};
+    // batch sizing
+    int64_t mem_budget = 0;  // bytes the per-batch arrays may take (0: the default share, mc_bp_plan.hpp)
+    size_t px_cap = 0;       // mask-pixel capacity of the per-batch arrays (pixel-list positions)
+    size_t fpx_cap = 0;      // frame-pixel capacity (the valid-id map)
+    double mfrac = 1.0;      // mask pixels per frame pixel a batch is sized for (the largest seen, + margin)
+    bool mfrac_obs = false;  // mfrac comes from an earlier call's batches (not the initial guess)
+    int last_fb = 0;         // frames per batch at the end of the last call
+    int64_t redo = 0;        // batches redone after a mask-pixel overflow (all calls)
+    // results of the last call
+    int F = 0, err_frame = -1;
+    int64_t nnz = 0;
+    DevBuf pts;  // the masks' point lists
+    std::vector<int32_t> col, label, stats;
+    std::vector<int64_t> off;
+};
+
 }  // namespace
 
 struct mc_ctx {
@@ -55,24 +114,11 @@ struct mc_ctx {
     bool own_stream = false;
     hipStream_t side = nullptr;                 // S3: workgroup-per-mask kernel beside the wave kernel
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t cls_stream[mc::kBpStreamClasses] = {};  // S1 denoise: the LDS size classes run side by side
-    hipEvent_t ev_cls[mc::kBpStreamClasses] = {};
     std::string err;
     mc::KernelTimer timer;
     int *h_stats = nullptr;  // pinned
-    int *h_bppack = nullptr;   // pinned per-batch S1 readback (k_bp_pack), h_bppack_n ints
-    int *h_bpstat = nullptr;   // pinned per-batch statistics block
-    hipEvent_t ev_pack = nullptr;  // the last batch's h_bppack copy (unpacked under the next batch)
-    size_t h_bppack_n = 0;
-    // pinned staging ring of mc_backproject_frames (two chunks, ping-pong)
-    char *h_stage[2] = {nullptr, nullptr};
-    size_t stage_bytes = 0;
-    hipEvent_t ev_stage[2] = {};
-    bool stage_used[2] = {false, false};
-    // host frames staged batch by batch on their own stream while the previous batch computes
-    hipStream_t copy = nullptr;
-    hipEvent_t ev_up = nullptr;
-    struct BpUpload *bp_up = nullptr;  // set for the duration of mc_backproject_frames' S1 call
+    int num_cu = 256;
+    BpState bp;  // S1 back-projection
 
     // ---- scene ----
     bool have_scene = false, have_graph = false, have_nodes = false, have_cluster = false;
@@ -112,40 +158,6 @@ struct mc_ctx {
     const unsigned long long *fin_vf = nullptr;
     int K = 0;
     int64_t npts = 0;
-
-    // ---- S1 back-projection ----
-    int64_t P_scene = 0;
-    bool have_points = false, have_bp = false;
-    float grid_radius = -1.f;  // scene grid built for this ball radius
-    unsigned gnb = 0;
-    DevBuf d_scene, d_gcnt, d_gstart, d_gbkt, d_gcellk, d_gpts, d_gidx, d_gcell, d_gscan_tmp;
-    DevBuf d_in_depth, d_in_seg, d_in_intr, d_in_pose, d_in_raw;
-    DevBuf d_band, d_present, d_fflags, d_cand, d_npix, d_csidx, d_poff, d_slot_of, d_bpstat;
-    DevBuf d_bpvid;  // per-batch valid-id map (k_bp_count -> k_bp_compact), 1 byte per pixel
-    DevBuf d_slot_frame, d_slot_id, d_slot_np, d_slot_pix, d_slot_nv, d_slot_m, d_slot_ns, d_slot_box, d_slot_nn,
-        d_slot_toff, d_slot_cov;
-    DevBuf d_pix_list, d_hkey, d_hvid, d_hfirst, d_vox_entry, d_acc, d_vpts, d_pcell, d_pbkt, d_bcnt, d_bstart,
-        d_blist, d_ncnt, d_par, d_droot, d_rnk, d_lab, d_ccnt, d_ssidx, d_avg, d_qpts;
-    DevBuf d_bpbm, d_tmp, d_kflag, d_ksize, d_midx, d_moff, d_out_col, d_out_label, d_out_off, d_out_pts, d_bp_pts;
-    DevBuf d_cls_list, d_nbl, d_lean, d_vox_order;  // denoise size-class slot lists; per-workgroup eps-neighbour lists, lean scratch
-    // voxel_down_sample: per-pixel voxel ids and voxel lists of k_bp_voxel_lds; its overflow slots
-    DevBuf d_vx_pvid, d_vx_list, d_vx_fb, d_bppack;
-    DevBuf d_scanm;  // block sums of the per-batch multi-workgroup scans
-    DevBuf d_slot_grid;  // denoise: grid origin / extent of the slots with points queued for the k-NN ring search
-    int num_cu = 256;
-    int64_t mem_budget = 0;  // bytes the S1 per-batch arrays may take (0: the default share, mc_backproject)
-    size_t bp_px_cap = 0;  // mask-pixel capacity of the per-batch arrays (pixel-list positions)
-    int bp_last_fb = 0;    // frames per batch at the end of the last mc_backproject
-    bool bp_mfrac_obs = false;  // bp_mfrac comes from an earlier call's batches (not the initial guess)
-    int64_t bp_redo = 0;   // batches redone after a mask-pixel overflow (all calls)
-    int bp_f_cap = 0;      // frame capacity of the per-batch arrays
-    size_t bp_fpx_cap = 0; // frame-pixel capacity (the valid-id map)
-    double bp_mfrac = 1.0; // mask pixels per frame pixel a batch is sized for (the largest seen, + margin)
-    int bp_bm_blocks = 0;
-    int bp_F = 0, bp_err_frame = -1;
-    int64_t bp_nnz = 0;
-    std::vector<int32_t> bp_col, bp_label, bp_stats;
-    std::vector<int64_t> bp_off;
 
     // ---- row-block sharding over processes ----
     int sh_rank = 0, sh_world = 1;
@@ -340,8 +352,8 @@ int mc_ctx_create(int device, mc_ctx **out)
         MC_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
         MC_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
         for (int c = 0; c < mc::kBpStreamClasses; c++) {
-            MC_HIP(hipStreamCreateWithFlags(&ctx->cls_stream[c], hipStreamNonBlocking));
-            MC_HIP(hipEventCreateWithFlags(&ctx->ev_cls[c], hipEventDisableTiming));
+            MC_HIP(hipStreamCreateWithFlags(&ctx->bp.cls_stream[c], hipStreamNonBlocking));
+            MC_HIP(hipEventCreateWithFlags(&ctx->bp.ev_cls[c], hipEventDisableTiming));
         }
         MC_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_stats), ST_COUNT * sizeof(int), hipHostMallocDefault));
         ctx->d_stats.reserve(ST_COUNT * sizeof(int));
@@ -366,58 +378,26 @@ void mc_ctx_destroy(mc_ctx *ctx)
         } catch (const McError &) {
         }
     }
-    DevBuf *bufs[] = {&ctx->d_mask_off, &ctx->d_mask_pts, &ctx->d_mask_col, &ctx->d_mask_label, &ctx->d_frame_start,
-                      &ctx->d_valid, &ctx->d_deg, &ctx->d_pt_off, &ctx->d_pt_list, &ctx->d_boundary,
-                      &ctx->d_pfm, &ctx->d_scan_tmp, &ctx->d_ctmp, &ctx->d_crow_len, &ctx->d_useg, &ctx->d_keep_cnt,
-                      &ctx->d_node_flag, &ctx->d_node_pos, &ctx->d_c_off, &ctx->d_c_idx, &ctx->d_vf, &ctx->d_hist, &ctx->d_s4rng,
-                      &ctx->d_thr, &ctx->d_isint, &ctx->d_stats, &ctx->d_node0_g, &ctx->d_n0_off, &ctx->d_n0_len,
-                      &ctx->d_n0_ptoff, &ctx->d_n0_ptlen, &ctx->d_n0_vf, &ctx->d_user_cidx, &ctx->d_user_pts,
-                      &ctx->d_parent, &ctx->d_root, &ctx->d_isroot, &ctx->d_rank, &ctx->d_label, &ctx->d_levels,
-                      &ctx->d_memcnt, &ctx->d_memoff, &ctx->d_ublen, &ctx->d_newoff, &ctx->d_members, &ctx->d_colcnt,
-                      &ctx->d_coloff, &ctx->d_colnodes, &ctx->d_ovf_n, &ctx->d_scratch,
-                      &ctx->d_touched, &ctx->d_edges, &ctx->d_spread, &ctx->d_Nlev, &ctx->d_final_label,
-                      &ctx->d_poolA, &ctx->d_poolB, &ctx->d_offA, &ctx->d_offB, &ctx->d_lenA, &ctx->d_lenB,
-                      &ctx->d_vfA, &ctx->d_vfB, &ctx->d_pmin, &ctx->d_pmax, &ctx->d_nwords, &ctx->d_woff,
-                      &ctx->d_bm, &ctx->d_ptcnt, &ctx->d_ptoff_out, &ctx->d_pts_out, &ctx->d_owner0,
-                      &ctx->d_node_of_mask, &ctx->d_ownA, &ctx->d_ownB, &ctx->d_cap, &ctx->d_obj_of_mask,
-                      &ctx->d_s3_small, &ctx->d_s3_big, &ctx->d_collen, &ctx->d_sh_eoff, &ctx->d_sh_send, &ctx->d_sh_recv, &ctx->d_sh_size,
-                      &ctx->d_cap_buf, &ctx->d_cap_cnt};
-    for (DevBuf *b : bufs) b->release();
-    DevBuf *bp_bufs[] = {&ctx->d_scene, &ctx->d_gcnt, &ctx->d_gstart, &ctx->d_gbkt, &ctx->d_gcellk, &ctx->d_gpts,
-                         &ctx->d_gidx, &ctx->d_gcell, &ctx->d_gscan_tmp, &ctx->d_in_depth, &ctx->d_in_seg, &ctx->d_in_raw,
-                         &ctx->d_in_intr, &ctx->d_in_pose, &ctx->d_band, &ctx->d_bpvid, &ctx->d_present, &ctx->d_fflags,
-                         &ctx->d_cand, &ctx->d_npix, &ctx->d_csidx, &ctx->d_poff, &ctx->d_slot_of, &ctx->d_bpstat,
-                         &ctx->d_slot_frame, &ctx->d_slot_id, &ctx->d_slot_np, &ctx->d_slot_pix, &ctx->d_slot_nv,
-                         &ctx->d_slot_m, &ctx->d_slot_ns, &ctx->d_slot_box, &ctx->d_slot_nn, &ctx->d_slot_toff,
-                         &ctx->d_slot_cov, &ctx->d_pix_list, &ctx->d_hkey, &ctx->d_hfirst,
-                         &ctx->d_vox_entry, &ctx->d_vpts, &ctx->d_pcell, &ctx->d_pbkt, &ctx->d_bcnt,
-                         &ctx->d_bstart, &ctx->d_blist, &ctx->d_ncnt, &ctx->d_par, &ctx->d_droot, &ctx->d_rnk,
-                         &ctx->d_lab, &ctx->d_ccnt, &ctx->d_ssidx, &ctx->d_avg, &ctx->d_qpts, &ctx->d_bpbm, &ctx->d_tmp,
-                         &ctx->d_kflag, &ctx->d_ksize, &ctx->d_midx, &ctx->d_moff, &ctx->d_out_col,
-                         &ctx->d_out_label, &ctx->d_out_off, &ctx->d_out_pts, &ctx->d_bp_pts,
-                         &ctx->d_cls_list, &ctx->d_nbl, &ctx->d_lean, &ctx->d_vox_order,
-                         &ctx->d_vx_pvid, &ctx->d_vx_list, &ctx->d_vx_fb, &ctx->d_bppack, &ctx->d_acc, &ctx->d_hvid,
-                         &ctx->d_slot_grid, &ctx->d_scanm};
-    for (DevBuf *b : bp_bufs) b->release();
-    if (ctx->copy) (void)hipStreamSynchronize(ctx->copy), (void)hipStreamDestroy(ctx->copy);
-    if (ctx->ev_up) (void)hipEventDestroy(ctx->ev_up);
+    BpState &bp = ctx->bp;
+    if (bp.copy) (void)hipStreamSynchronize(bp.copy), (void)hipStreamDestroy(bp.copy);
+    if (bp.ev_up) (void)hipEventDestroy(bp.ev_up);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
-    if (ctx->h_bppack) (void)hipHostFree(ctx->h_bppack);
-    if (ctx->h_bpstat) (void)hipHostFree(ctx->h_bpstat);
-    if (ctx->ev_pack) (void)hipEventDestroy(ctx->ev_pack);
+    if (bp.h_pack) (void)hipHostFree(bp.h_pack);
+    if (bp.h_stat) (void)hipHostFree(bp.h_stat);
+    if (bp.ev_pack) (void)hipEventDestroy(bp.ev_pack);
     for (int b = 0; b < 2; b++) {
-        if (ctx->h_stage[b]) (void)hipHostFree(ctx->h_stage[b]);
-        if (ctx->ev_stage[b]) (void)hipEventDestroy(ctx->ev_stage[b]);
+        if (bp.h_stage[b]) (void)hipHostFree(bp.h_stage[b]);
+        if (bp.ev_stage[b]) (void)hipEventDestroy(bp.ev_stage[b]);
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->side) (void)hipStreamSynchronize(ctx->side), (void)hipStreamDestroy(ctx->side);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     for (int c = 0; c < mc::kBpStreamClasses; c++) {
-        if (ctx->cls_stream[c]) (void)hipStreamSynchronize(ctx->cls_stream[c]), (void)hipStreamDestroy(ctx->cls_stream[c]);
-        if (ctx->ev_cls[c]) (void)hipEventDestroy(ctx->ev_cls[c]);
+        if (bp.cls_stream[c]) (void)hipStreamSynchronize(bp.cls_stream[c]), (void)hipStreamDestroy(bp.cls_stream[c]);
+        if (bp.ev_cls[c]) (void)hipEventDestroy(bp.ev_cls[c]);
     }
-    delete ctx;
+    delete ctx;  // every DevBuf frees its memory in its destructor, after the streams above are drained
 }
 
 int mc_ctx_set_stream(mc_ctx *ctx, void *hip_stream)
@@ -489,7 +469,7 @@ int mc_ctx_set_memory_budget(mc_ctx *ctx, int64_t bytes)
 {
     return guarded(ctx, [&] {
         MC_REQUIRE(bytes >= 0, MC_ERR_INVALID, "negative memory budget");
-        ctx->mem_budget = bytes;
+        ctx->bp.mem_budget = bytes;
     });
 }
 
@@ -1734,927 +1714,13 @@ int mc_cluster_get_objects(mc_ctx *ctx, uint64_t *vf_bits, int64_t *c_off, int32
     });
 }
 
-// ---------------------------------------------------------------------------------------------
-// S1 back-projection
-// ---------------------------------------------------------------------------------------------
-__global__ void k_fill_u32(unsigned *p, size_t n, unsigned v)
-{
-    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256) p[i] = v;
-}
-
 }  // extern "C"
 
-namespace {
-
-void fill_u32(hipStream_t s, void *p, size_t n, unsigned v)
-{
-    if (n) hipLaunchKernelGGL(k_fill_u32, grid_for(static_cast<int64_t>(n)), dim3(256), 0, s, static_cast<unsigned *>(p), n, v);
-}
-
-// grow a device buffer, keeping its first `used` bytes
-void grow_keep(DevBuf &b, size_t bytes, size_t used, hipStream_t s)
-{
-    if (bytes <= b.bytes) return;
-    DevBuf nb;
-    nb.reserve(bytes + bytes / 2);
-    if (used) MC_HIP(hipMemcpyAsync(nb.ptr, b.ptr, used, hipMemcpyDeviceToDevice, s));
-    MC_HIP(hipStreamSynchronize(s));
-    b.swap(nb);  // the old buffer is freed with nb
-}
-
-enum BpStat : int {
-    BS_ERRF = 0, BS_VOXERR, BS_OVF, BS_TOP, BS_NS, BS_NPX, BS_M, BS_NNZ,
-    BS_CLS,             // denoise size-class counts (kBpClasses LDS classes + the global-memory kernel)
-    BS_TK = BS_CLS + mc::kBpClasses + 1,  // ticket counters of the LDS classes
-    BS_VXFB = BS_TK + mc::kBpClasses,     // slots the first voxel tier hands to the second
-    BS_VXFB2,                             // slots the second voxel tier hands to k_bp_voxel
-    BS_DQ,                                // points queued for the k-NN ring search
-    BS_DNERR,                             // denoise internal-error bits (queue entry / region out of range)
-    BS_PXOVF,                             // the batch's mask pixels exceed the capacity: grown, batch redone
-    BS_COUNT
-};
-
-size_t slots_cap(int fb) { return static_cast<size_t>(fb) * 256 + 1; }  // (frame, id) slots of a batch
-// HBM of the per-batch S1 arrays (bp_reserve): per mask pixel (the arrays indexed by pixel-list position,
-// voxel and point arrays included: 195 B) and per frame pixel (the valid-id map); the per-slot and
-// per-frame ones are small against them.  A batch's frames are sized for its mask pixels: the share of
-// mask pixels among frame pixels seen so far (bp_mfrac, 1 before any batch) decides the frames per batch,
-// and a batch with more mask pixels than its capacity grows the arrays and is redone.
-constexpr size_t kBpBytesPerMaskPixel = 196;
-constexpr size_t kBpBytesPerFramePixel = 2;
-
-// (re)allocate the per-batch arrays for fb frames of H x W (pixel capacity fb*H*W)
-// Workgroups per resident slot of a denoise class (the classes take slots from tickets): the extra
-// ones start on CUs that other classes free, so no class keeps only its initial share of the chip.
-#ifndef MC_BP_OVERSUB
-#define MC_BP_OVERSUB 2
-#endif
-constexpr int kBpOversub = MC_BP_OVERSUB;  // class grids: resident workgroups x this (slots come from tickets)
-// u16 entries of per-workgroup eps-neighbour lists before class cls's region
-inline size_t nbl_offset(const mc_ctx *ctx, int cls)
-{
-    const size_t per_cls[mc::kBpClasses] = {static_cast<size_t>(mc::BpLdsClass<512>::kWgPerCu) * 512,
-                                            static_cast<size_t>(mc::BpLdsClass<1024>::kWgPerCu) * 1024,
-                                            static_cast<size_t>(mc::BpLdsClass<2048>::kWgPerCu) * 2048,
-                                            static_cast<size_t>(mc::BpLdsClass<3072>::kWgPerCu) * 3072,
-                                            static_cast<size_t>(mc::BpLdsClass<4096>::kWgPerCu) * 4096,
-                                            static_cast<size_t>(mc::BpLdsClass<16384>::kWgPerCu) * 16384};
-    size_t o = 0;
-    for (int c = 0; c < cls; c++) o += per_cls[c];
-    return o * static_cast<size_t>(ctx->num_cu) * kBpOversub * mc::kBpNbCap;
-}
-
-// ints of per-workgroup lean scratch before class cls's region
-inline size_t lean_offset(const mc_ctx *ctx, int cls)
-{
-    const size_t per_cls[mc::kBpClasses] = {
-        mc::kBpLeanInts<512> * mc::BpLdsClass<512>::kWgPerCu, mc::kBpLeanInts<1024> * mc::BpLdsClass<1024>::kWgPerCu,
-        mc::kBpLeanInts<2048> * mc::BpLdsClass<2048>::kWgPerCu, mc::kBpLeanInts<3072> * mc::BpLdsClass<3072>::kWgPerCu,
-        mc::kBpLeanInts<4096> * mc::BpLdsClass<4096>::kWgPerCu,
-        mc::kBpLeanInts<16384> * mc::BpLdsClass<16384>::kWgPerCu};
-    size_t o = 0;
-    for (int c = 0; c < cls; c++) o += per_cls[c];
-    return o * static_cast<size_t>(ctx->num_cu) * kBpOversub;
-}
-
-void bp_reserve(mc_ctx *ctx, int fb, int H, int W, int nbands, size_t mask_px, hipStream_t s)
-{
-    const size_t px = mask_px + 1;
-    const size_t slots = slots_cap(fb);
-    ctx->d_band.reserve(static_cast<size_t>(fb) * nbands * mc::kBpWaves * 256 * 4);
-    ctx->d_bpvid.reserve(static_cast<size_t>(fb) * H * W + 16);
-    ctx->bp_fpx_cap = std::max(ctx->bp_fpx_cap, static_cast<size_t>(fb) * H * W);
-    ctx->d_present.reserve(static_cast<size_t>(fb) * 8 * 4);
-    ctx->d_fflags.reserve(static_cast<size_t>(fb) * 4);
-    ctx->d_cand.reserve(slots * 4);
-    ctx->d_npix.reserve(slots * 4);
-    ctx->d_csidx.reserve((slots + 1) * 4);
-    ctx->d_poff.reserve((slots + 1) * 4);
-    ctx->d_slot_of.reserve(slots * 4);
-    ctx->d_bpstat.reserve(BS_COUNT * 4);
-    DevBuf *sl[] = {&ctx->d_slot_frame, &ctx->d_slot_id, &ctx->d_slot_np, &ctx->d_slot_pix, &ctx->d_slot_nv,
-                    &ctx->d_slot_m,     &ctx->d_slot_ns, &ctx->d_slot_nn, &ctx->d_slot_toff, &ctx->d_slot_cov,
-                    &ctx->d_kflag,      &ctx->d_ksize};
-    for (DevBuf *b : sl) b->reserve(slots * 4);
-    ctx->d_midx.reserve((slots + 1) * 4);
-    ctx->d_moff.reserve((slots + 1) * 4);
-    ctx->d_slot_box.reserve(slots * 6 * 4);
-    ctx->d_cls_list.reserve((mc::kBpClasses + 1) * slots * 4);
-    ctx->d_vox_order.reserve(slots * 4);
-    ctx->d_vx_fb.reserve(2 * slots * 4);  // the two tiers' overflow lists
-    ctx->d_scanm.reserve(4 * (slots / mc::kScanTile + 3) * 4);
-    ctx->d_slot_grid.reserve(8 * slots * 8);
-    // per-workgroup eps-neighbour lists, one region per size class (the classes run concurrently)
-    ctx->d_nbl.reserve(nbl_offset(ctx, mc::kBpClasses) * 2);
-    ctx->d_lean.reserve(lean_offset(ctx, mc::kBpClasses) * 4);
-    if (ctx->bp_px_cap < px) {
-        ctx->d_pix_list.reserve(px * 4);
-        ctx->d_hkey.reserve(2 * px * 8);
-        ctx->d_hvid.reserve(2 * px * 4);
-        ctx->d_hfirst.reserve(2 * px * 4);
-        fill_u32(s, ctx->d_hkey.ptr, 4 * px, 0xFFFFFFFFu);  // empty key, kept empty by k_bp_voxel
-        fill_u32(s, ctx->d_hvid.ptr, 2 * px, 0xFFFFFFFFu);  // -1
-        fill_u32(s, ctx->d_hfirst.ptr, 2 * px, 0x7FFFFFFFu);  // INT_MAX
-        ctx->d_acc.reserve(px * 4 * 8);
-        ctx->d_vx_pvid.reserve(px * 4);
-        ctx->d_vx_list.reserve(px * 4);
-        ctx->d_vox_entry.reserve(px * 4);
-        ctx->d_vpts.reserve(px * 3 * 8);
-        ctx->d_pcell.reserve(px * 8);
-        ctx->d_pbkt.reserve(px * 4);
-        ctx->d_bcnt.reserve(2 * px * 4);
-        fill_u32(s, ctx->d_bcnt.ptr, 2 * px, 0u);  // kept zero by k_bp_denoise
-        ctx->d_bstart.reserve((2 * px + slots + 1) * 4);
-        ctx->d_blist.reserve(px * 4);
-        ctx->d_ncnt.reserve(px * 4);
-        ctx->d_par.reserve(px * 4);
-        ctx->d_droot.reserve(px * 4);
-        ctx->d_rnk.reserve(px * 4);
-        ctx->d_lab.reserve(px * 4);
-        ctx->d_ccnt.reserve((px + slots + 1) * 4);
-        ctx->d_ssidx.reserve(px * 4);
-        ctx->d_avg.reserve(px * 8);
-        ctx->d_qpts.reserve(px * 3 * 4);
-        ctx->bp_px_cap = px;
-    }
-    ctx->bp_f_cap = std::max(ctx->bp_f_cap, fb);
-}
-
-void bp_build_grid(mc_ctx *ctx, float radius, hipStream_t s)
-{
-    const int P = static_cast<int>(ctx->P_scene);
-    const float inv = 1.0f / (2.0f * radius);
-    const unsigned nb = static_cast<unsigned>(std::max(2 * P, 16));
-    ctx->gnb = nb;
-    const bool fresh = ctx->d_gcnt.bytes < (nb + 1) * 4ull;
-    ctx->d_gcnt.reserve((nb + 1) * 4ull);
-    if (fresh) MC_HIP(hipMemsetAsync(ctx->d_gcnt.ptr, 0, ctx->d_gcnt.bytes, s));  // kept zero by k_grid_scatter
-    ctx->d_gstart.reserve((nb + 2) * 4ull);
-    ctx->d_gbkt.reserve((P + 1) * 4ull);
-    ctx->d_gcellk.reserve((P + 1) * 8ull);
-    ctx->d_gpts.reserve((P + 1) * 16ull);
-    ctx->d_gidx.reserve((P + 1) * 4ull);
-    ctx->d_gcell.reserve((P + 1) * 8ull);
-    ctx->d_gscan_tmp.reserve((2 * (nb / mc::kScanTile + 4) + 16) * 4ull);
-    if (P) {
-        hipLaunchKernelGGL(mc::k_grid_count, grid_for(P), dim3(256), 0, s, ctx->d_scene.as<float>(), P, inv, nb,
-                           ctx->d_gcnt.as<int>(), ctx->d_gbkt.as<unsigned>(), ctx->d_gcellk.as<unsigned long long>());
-    }
-    mc::scan_large(s, ctx->d_gcnt.as<int>(), ctx->d_gstart.as<int>(), static_cast<int>(nb), ctx->d_gscan_tmp.as<int>());
-    if (P)
-        hipLaunchKernelGGL(mc::k_grid_scatter, grid_for(P), dim3(256), 0, s, ctx->d_scene.as<float>(), P,
-                           ctx->d_gbkt.as<unsigned>(), ctx->d_gcellk.as<unsigned long long>(), ctx->d_gstart.as<int>(),
-                           ctx->d_gcnt.as<int>(), ctx->d_gpts.as<float4>(), ctx->d_gidx.as<int>(),
-                           ctx->d_gcell.as<unsigned long long>());
-    ctx->grid_radius = radius;
-}
-
-
-// one LDS size class of the denoise: as many workgroups as are resident at once, each taking the
-// class's slots from a ticket counter
-// The k-NN ring search (k_bp_knn_ring) and the statistics / survivors (k_bp_denoise_tail) of every LDS
-// class, once after the classes join, over one queue (queued per class behind each class kernel they
-// measured 2 % slower at C3: the concurrent ring searches competed with the remaining classes,
-// profiles/r04/r4e_tail_ab.jsonl)
-void bp_denoise_tail_launch(mc_ctx *ctx, hipStream_t s, int ncap, int *st, const mc::BpDev &dv)
-{
-    auto ring = [&](auto kern, int wg_per_cu) {
-        hipLaunchKernelGGL(kern, dim3(ctx->num_cu * wg_per_cu), dim3(256), 0, s, st + BS_DQ,
-                           ctx->d_vx_pvid.as<int>(), ctx->d_slot_pix.as<int>(), ctx->d_slot_m.as<int>(), dv,
-                           ctx->d_acc.as<double4>(), ctx->d_bstart.as<int>(), ctx->d_vx_list.as<int>(),
-                           ctx->d_slot_grid.as<double>(), ctx->d_avg.as<double>(), st + BS_DNERR);
-    };
-    ring(mc::k_bp_knn_ring<4>, 8);  // (four waves per SIMD; at five or six, spilling: no faster)
-    // a wave per slot whose ordered sums wait on latency: as many waves as its 45 VGPRs allow
-    const int tail_wg = getenv("MC_BP_TAILWG") ? atoi(getenv("MC_BP_TAILWG")) : 8;
-    hipLaunchKernelGGL(mc::k_bp_denoise_tail, dim3(ctx->num_cu * tail_wg), dim3(256), 0, s,
-                       st + BS_CLS, ctx->d_cls_list.as<int>(), ncap, 0, mc::kBpClasses, ctx->d_slot_pix.as<int>(),
-                       ctx->d_slot_m.as<int>(), dv, ctx->d_vpts.as<double>(), ctx->d_avg.as<double>(),
-                       ctx->d_ssidx.as<int>(), ctx->d_qpts.as<float>(), ctx->d_slot_ns.as<int>(),
-                       ctx->d_slot_box.as<float>());
-}
-
-template <int N>
-void bp_denoise_class(mc_ctx *ctx, hipStream_t s, int cls, int ncap, int *st, const mc::BpDev &dv)
-{
-    using C = mc::BpLdsClass<N>;
-    // the classes run concurrently: each has its own region of per-workgroup neighbour lists
-    hipLaunchKernelGGL(mc::k_bp_denoise_lds<N>, dim3(ctx->num_cu * C::kWgPerCu * kBpOversub), dim3(C::T), 0, s, st + BS_CLS + cls,
-                       ctx->d_cls_list.as<int>() + static_cast<size_t>(cls) * ncap, st + BS_TK + cls,
-                       ctx->d_slot_pix.as<int>(), ctx->d_slot_nv.as<int>(), dv, ctx->d_vpts.as<double>(),
-                       ctx->d_nbl.as<unsigned short>() + nbl_offset(ctx, cls), ctx->d_lean.as<int>() + lean_offset(ctx, cls),
-                       ctx->d_slot_m.as<int>(), ctx->d_avg.as<double>(), ctx->d_ssidx.as<int>(),
-                       ctx->d_acc.as<double4>(), ctx->d_bstart.as<int>(), ctx->d_vx_list.as<int>(),
-                       ctx->d_vx_pvid.as<int>(), st + BS_DQ, static_cast<int>(std::min<size_t>(ctx->bp_px_cap, INT_MAX)),
-                       ctx->d_slot_grid.as<double>(), st + BS_DNERR);
-}
-// MC_BP_DEBUG_SYNC=1: synchronise and report after every S1 group (diagnostics of a stalled batch)
-void bp_debug_sync(hipStream_t s, const char *what)
-{
-    static const bool on = getenv("MC_BP_DEBUG_SYNC") != nullptr;
-    if (!on) return;
-    fprintf(stderr, "[mc bp] %s issued\n", what);
-    MC_HIP(hipStreamSynchronize(s));
-    MC_HIP(hipDeviceSynchronize());
-    fprintf(stderr, "[mc bp] %s done\n", what);
-}
-
-}  // namespace
-
-extern "C" {
-
-void mc_bp_params_default(mc_bp_params *p)
-{
-    if (!p) return;
-    p->depth_trunc = 20.0;
-    p->voxel_size = 0.01;
-    p->dbscan_eps = 0.04;
-    p->component_min_fraction = 0.2;
-    p->sor_std_ratio = 2.0;
-    p->ball_radius = 0.01;
-    p->coverage_threshold = 0.3;
-    p->dbscan_min_points = 4;
-    p->sor_neighbors = 20;
-    p->ball_k = 20;
-    p->few_points = 25;
-}
-
-int mc_scene_set_points(mc_ctx *ctx, int64_t num_points, const float *xyz, int on_device)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(num_points >= 0 && num_points < (int64_t(1) << 31) - 1, MC_ERR_UNSUPPORTED, "num_points out of range");
-        MC_REQUIRE(num_points == 0 || xyz, MC_ERR_INVALID, "null points");
-        hipStream_t s = ctx->stream;
-        ctx->P_scene = num_points;
-        ctx->d_scene.reserve((num_points + 1) * 12);
-        if (num_points)
-            MC_HIP(hipMemcpyAsync(ctx->d_scene.ptr, xyz, num_points * 12,
-                                  on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        ctx->have_points = true;
-        ctx->have_bp = false;
-        ctx->grid_radius = -1.f;  // the grid is built by the next mc_backproject
-        MC_HIP(hipStreamSynchronize(s));
-    });
-}
-
-// Per-frame host arrays -> one device array [F, frame_bytes]: the frames are copied by host
-// threads into a pinned chunk while the previous chunk's DMA runs (pageable hipMemcpy would stage
-// through the runtime's own buffers on one thread, and np.stack would add a full host copy).
-// host frames of one mc_backproject_frames call; frames [0, staged) are on the device (or queued
-// on ctx->copy before ctx->ev_up)
-struct BpUpload {
-    const void *const *depth;
-    const void *const *seg;
-    int staged;
-    double raw_scale;  // > 0: depth frames are the PNGs' uint16 values, decoded on the copy stream
-};
-
-// frames [f_lo, f_hi) (frames[f] = host pointer of frame f) -> dst + f * frame_bytes, through the
-// pinned ping-pong chunks: host threads fill one chunk while the DMA of the other runs on stream s
-static void stage_frames(mc_ctx *ctx, const void *const *frames, size_t frame_bytes, int f_lo, int f_hi, char *dst,
-                         hipStream_t s)
-{
-    if (f_hi <= f_lo || !frame_bytes) return;
-    const size_t want = std::max<size_t>(frame_bytes, static_cast<size_t>(32) << 20);
-    if (ctx->stage_bytes < want) {
-        for (int b = 0; b < 2; b++) {
-            if (ctx->stage_used[b]) MC_HIP(hipEventSynchronize(ctx->ev_stage[b]));
-            if (ctx->h_stage[b]) MC_HIP(hipHostFree(ctx->h_stage[b]));
-            ctx->h_stage[b] = nullptr;
-            ctx->stage_used[b] = false;
-        }
-        ctx->stage_bytes = 0;
-        for (int b = 0; b < 2; b++) {
-            MC_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_stage[b]), want, hipHostMallocDefault));
-            if (!ctx->ev_stage[b]) MC_HIP(hipEventCreateWithFlags(&ctx->ev_stage[b], hipEventDisableTiming));
-        }
-        ctx->stage_bytes = want;
-    }
-    int nthreads = static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())));
-    if (const char *e = getenv("MC_STAGE_THREADS")) nthreads = std::max(1, std::min(64, atoi(e)));
-    const int per = static_cast<int>(std::max<size_t>(1, ctx->stage_bytes / frame_bytes));
-    int b = 0;
-    for (int f0 = f_lo; f0 < f_hi; f0 += per, b ^= 1) {
-        const int n = std::min(per, f_hi - f0);
-        if (ctx->stage_used[b]) MC_HIP(hipEventSynchronize(ctx->ev_stage[b]));  // its last DMA is done
-        char *buf = ctx->h_stage[b];
-        const size_t total = static_cast<size_t>(n) * frame_bytes;
-        auto copy_range = [&](size_t lo, size_t hi) {
-            while (lo < hi) {
-                const size_t f = lo / frame_bytes, o = lo % frame_bytes;
-                const size_t len = std::min(hi - lo, frame_bytes - o);
-                memcpy(buf + lo, static_cast<const char *>(frames[f0 + f]) + o, len);
-                lo += len;
-            }
-        };
-        const int nt = static_cast<int>(std::min<size_t>(nthreads, std::max<size_t>(1, total >> 22)));  // >= 4 MB each
-        if (nt <= 1) {
-            copy_range(0, total);
-        } else {
-            std::vector<std::thread> th;
-            const size_t step = (total + nt - 1) / nt;
-            for (int t = 1; t < nt; t++) th.emplace_back(copy_range, std::min(total, t * step), std::min(total, (t + 1) * step));
-            copy_range(0, std::min(total, step));
-            for (auto &x : th) x.join();
-        }
-        MC_HIP(hipMemcpyAsync(dst + static_cast<size_t>(f0) * frame_bytes, buf, total, hipMemcpyHostToDevice, s));
-        MC_HIP(hipEventRecord(ctx->ev_stage[b], s));
-        ctx->stage_used[b] = true;
-    }
-}
-
-static int backproject_frames_impl(mc_ctx *ctx, int32_t num_frames, int32_t height, int32_t width,
-                                   const void *const *depth_frames, double raw_scale, const uint8_t *const *seg_frames,
-                                   const double *intrinsics, const double *poses, const mc_bp_params *params)
-{
-    const int rc = guarded(ctx, [&] {
-        MC_REQUIRE(raw_scale >= 0.0 && std::isfinite(raw_scale), MC_ERR_INVALID, "bad depth_scale");
-        MC_REQUIRE(num_frames >= 0 && height > 0 && width > 0, MC_ERR_INVALID, "bad frame sizes");
-        MC_REQUIRE(num_frames == 0 || (depth_frames && seg_frames && intrinsics && poses), MC_ERR_INVALID,
-                   "null frame arrays");
-        for (int f = 0; f < num_frames; f++)
-            MC_REQUIRE(depth_frames[f] && seg_frames[f], MC_ERR_INVALID, "null frame array");
-        const int F = num_frames;
-        const size_t HW = static_cast<size_t>(height) * width;
-        if (!F) return;
-        hipStream_t s = ctx->stream;
-        ctx->d_in_depth.reserve(F * HW * 4);
-        ctx->d_in_seg.reserve(F * HW);
-        if (raw_scale > 0.0) ctx->d_in_raw.reserve(F * HW * 2);
-        ctx->d_in_intr.reserve(F * 4 * 8ull);
-        ctx->d_in_pose.reserve(F * 16 * 8ull);
-        MC_HIP(hipMemcpyAsync(ctx->d_in_intr.ptr, intrinsics, F * 4 * 8ull, hipMemcpyHostToDevice, s));
-        MC_HIP(hipMemcpyAsync(ctx->d_in_pose.ptr, poses, F * 16 * 8ull, hipMemcpyHostToDevice, s));
-        if (!ctx->copy) {
-            MC_HIP(hipStreamCreateWithFlags(&ctx->copy, hipStreamNonBlocking));
-            MC_HIP(hipEventCreateWithFlags(&ctx->ev_up, hipEventDisableTiming));
-        }
-    });
-    if (rc != MC_OK) return rc;
-    if (!num_frames) {
-        static const float zf = 0.f;
-        static const uint8_t zs = 0;
-        static const double zd[16] = {};
-        return mc_backproject(ctx, 0, height, width, &zf, &zs, zd, zd, 0, params);
-    }
-    // the frames are staged by the S1 batch loop itself: batch b + 1's while batch b computes
-    BpUpload up{depth_frames, reinterpret_cast<const void *const *>(seg_frames), 0, raw_scale};
-    ctx->bp_up = &up;
-    const int rc2 = mc_backproject(ctx, num_frames, height, width, ctx->d_in_depth.as<float>(),
-                                   ctx->d_in_seg.as<uint8_t>(), ctx->d_in_intr.as<double>(),
-                                   ctx->d_in_pose.as<double>(), 1, params);
-    ctx->bp_up = nullptr;
-    (void)hipStreamSynchronize(ctx->copy);  // no DMA into d_in_* outlives the call (error paths)
-    return rc2;
-}
-
-int mc_backproject_frames(mc_ctx *ctx, int32_t num_frames, int32_t height, int32_t width,
-                          const float *const *depth_frames, const uint8_t *const *seg_frames,
-                          const double *intrinsics, const double *poses, const mc_bp_params *params)
-{
-    return backproject_frames_impl(ctx, num_frames, height, width, reinterpret_cast<const void *const *>(depth_frames),
-                                   0.0, seg_frames, intrinsics, poses, params);
-}
-
-int mc_backproject_frames_raw(mc_ctx *ctx, int32_t num_frames, int32_t height, int32_t width,
-                              const uint16_t *const *depth_frames, double depth_scale,
-                              const uint8_t *const *seg_frames, const double *intrinsics, const double *poses,
-                              const mc_bp_params *params)
-{
-    if (!(depth_scale > 0.0)) return guarded(ctx, [&] { MC_REQUIRE(false, MC_ERR_INVALID, "depth_scale must be > 0"); });
-    return backproject_frames_impl(ctx, num_frames, height, width, reinterpret_cast<const void *const *>(depth_frames),
-                                   depth_scale, seg_frames, intrinsics, poses, params);
-}
-
-int mc_backproject(mc_ctx *ctx, int32_t num_frames, int32_t height, int32_t width, const float *depth,
-                   const uint8_t *seg, const double *intrinsics, const double *poses, int on_device,
-                   const mc_bp_params *params)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_points, MC_ERR_STATE, "mc_backproject before mc_scene_set_points");
-        MC_REQUIRE(num_frames >= 0 && height > 0 && width > 0, MC_ERR_INVALID, "bad frame sizes");
-        MC_REQUIRE(num_frames == 0 || (depth && seg && intrinsics && poses), MC_ERR_INVALID, "null frame arrays");
-        MC_REQUIRE(static_cast<int64_t>(height) * width < (int64_t(1) << 31), MC_ERR_UNSUPPORTED, "image too large");
-        mc_bp_params prm;
-        if (params) prm = *params;
-        else mc_bp_params_default(&prm);
-        MC_REQUIRE(prm.sor_neighbors >= 1 && prm.sor_neighbors <= mc::kBpKnnMax, MC_ERR_UNSUPPORTED,
-                   "sor_neighbors must be in [1, 20]");
-        MC_REQUIRE(prm.ball_k >= 1 && prm.ball_k <= mc::kBpBallMax, MC_ERR_UNSUPPORTED, "ball_k must be in [1, 32]");
-        MC_REQUIRE(prm.voxel_size > 0 && prm.dbscan_eps > 0 && prm.ball_radius > 0, MC_ERR_INVALID, "bad radii");
-        hipStream_t s = ctx->stream;
-        const int F = num_frames, H = height, W = width;
-        const size_t HW = static_cast<size_t>(H) * W;
-        const int nbands = (H + mc::kBpBand - 1) / mc::kBpBand;
-        ctx->have_bp = false;
-        ctx->bp_F = F;
-        ctx->bp_err_frame = -1;
-        ctx->bp_col.clear();
-        ctx->bp_label.clear();
-        ctx->bp_off.assign(1, 0);
-        ctx->bp_stats.clear();
-        ctx->bp_nnz = 0;
-        const float rf = static_cast<float>(prm.ball_radius);
-        if (ctx->grid_radius != rf) {  // a new scene (mc_scene_set_points) or radius: the 2r scene grid
-            TimedScope ts(ctx->timer, s, "bp_grid");
-            bp_build_grid(ctx, rf, s);
-        }
-
-        const float *dep = depth;
-        const uint8_t *sg = seg;
-        const double *Kp = intrinsics, *Tp = poses;
-        if (!on_device && F) {
-            ctx->d_in_depth.reserve(F * HW * 4);
-            ctx->d_in_seg.reserve(F * HW);
-            ctx->d_in_intr.reserve(F * 4 * 8ull);
-            ctx->d_in_pose.reserve(F * 16 * 8ull);
-            MC_HIP(hipMemcpyAsync(ctx->d_in_depth.ptr, depth, F * HW * 4, hipMemcpyHostToDevice, s));
-            MC_HIP(hipMemcpyAsync(ctx->d_in_seg.ptr, seg, F * HW, hipMemcpyHostToDevice, s));
-            MC_HIP(hipMemcpyAsync(ctx->d_in_intr.ptr, intrinsics, F * 4 * 8ull, hipMemcpyHostToDevice, s));
-            MC_HIP(hipMemcpyAsync(ctx->d_in_pose.ptr, poses, F * 16 * 8ull, hipMemcpyHostToDevice, s));
-            dep = ctx->d_in_depth.as<float>();
-            sg = ctx->d_in_seg.as<uint8_t>();
-            Kp = ctx->d_in_intr.as<double>();
-            Tp = ctx->d_in_pose.as<double>();
-        }
-        // test knob: smallest denoise size class (0 = by size; 3 = the lean LDS class, 4 = the
-        // global-memory kernel for every slot)
-        int min_cls = 0;
-        if (const char *e = getenv("MC_BP_MIN_CLASS")) min_cls = std::min(mc::kBpClasses, std::max(0, atoi(e)));
-        // test knob: MC_VX_GLOBAL=1 hands every slot to the global-hash voxel kernel, =2 to the second
-        // LDS tier
-        const int vx_global = getenv("MC_VX_GLOBAL") ? atoi(getenv("MC_VX_GLOBAL")) : 0;
-        // frames per batch: bounded pixel capacity of the per-slot arrays (≈ 200 B of per-batch arrays
-        // per pixel).  Large batches amortise every group's slot tail and the per-batch sync (C3 E2E:
-        // 192 M pixels 215 ms, 400 M 184 ms, 600 M 175 ms per scene in round 2; 1 G 115 ms against
-        // 118 ms at the old 640 M / 45 % cap in round 3, profiles/r03/ab19_batch_pixels.jsonl), so the
-        // batch takes up to 1 G pixels or 65 % of the free HBM (≈ 170 GB of a fresh 288 GB device),
-        // whichever is less; the frames are then dealt into equal batches, so that no batch is a small
-        // remainder with its own tails
-        // The per-batch arrays take at most the context's HBM budget (mc_ctx_set_memory_budget), by
-        // default 40 % of the device or 65 % of what is free (plus what this context already holds),
-        // whichever is less, so a caller's own allocator keeps room (a fresh 288 GB MI355X: ~115 GB,
-        // ~530 M pixels per batch); a caller that owns the device (bench.py) sets a larger one.
-        // frame pixels per batch: below 2^31 (int positions), and within the byte budget at the
-        // expected mask-pixel share (C3: 0.23 of the frame pixels, so two batches instead of six; the
-        // per-batch tails and syncs cost ~3 ms each, profiles/r05/r5s_*)
-        size_t budget = (static_cast<size_t>(1) << 31) - 1;
-        // test knob: MC_BP_MASK_FRAC sets the expected share (a small one forces the grow-and-redo path)
-        if (const char *e = getenv("MC_BP_MASK_FRAC")) ctx->bp_mfrac = atof(e);
-        const double mfrac = std::min(1.0, std::max(ctx->bp_mfrac, 1e-4));
-        size_t bud_bytes = 0;  // the per-batch arrays' byte budget (also bounds the grow-and-redo below)
-        {
-            const size_t held = ctx->bp_px_cap * kBpBytesPerMaskPixel + ctx->bp_fpx_cap * kBpBytesPerFramePixel;
-            size_t bytes = static_cast<size_t>(ctx->mem_budget);
-            if (ctx->mem_budget <= 0) {
-                size_t free_b = 0, total_b = 0;
-                bytes = held;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b)
-                    bytes = std::min(total_b / 100 * 40, (free_b + held) / 100 * 65);
-            }
-            bud_bytes = bytes;
-            const double per_px = static_cast<double>(kBpBytesPerFramePixel) + mfrac * kBpBytesPerMaskPixel;
-            budget = std::max<size_t>(HW, std::min(budget, static_cast<size_t>(static_cast<double>(bytes) / per_px)));
-        }
-        const bool fixed_batch = getenv("MC_BP_BATCH_PIXELS") != nullptr;
-        if (const char *e = getenv("MC_BP_BATCH_PIXELS")) budget = std::max<size_t>(1, strtoull(e, nullptr, 10));
-        BpUpload *const up = on_device ? ctx->bp_up : nullptr;
-        int FB = static_cast<int>(std::max<size_t>(1, std::min<size_t>(std::max(F, 1), budget / HW)));
-        {
-            const int nb = (std::max(F, 1) + FB - 1) / FB;
-            FB = (std::max(F, 1) + nb - 1) / nb;
-        }
-        // frames arriving from the host: batch b + 1's upload runs under batch b's compute.  Splitting a
-        // scene that fits one batch into more batches only to overlap its upload did not pay (C2 API
-        // path: 1 batch 44.9 ms, 8 batches 46.2 ms, profiles/r03/api/), so by default only scenes of
-        // several batches overlap (C3: 7); MC_BP_UPLOAD_BATCHES=n forces at least n batches
-        if (up) {
-            int nb = 1;
-            if (const char *e = getenv("MC_BP_UPLOAD_BATCHES")) nb = std::max(1, atoi(e));
-            FB = std::max(1, std::min(FB, (F + nb - 1) / nb));
-        }
-        // stage the host frames [up->staged, f_hi) on the copy stream
-        auto upload_to = [&](int f_hi) {
-            if (!up || f_hi <= up->staged) return;
-            if (up->raw_scale > 0.0) {  // 2-byte frames, then float32(u16 / scale) on the copy stream
-                stage_frames(ctx, up->depth, HW * 2, up->staged, f_hi, static_cast<char *>(ctx->d_in_raw.ptr), ctx->copy);
-                const int64_t total = static_cast<int64_t>(f_hi - up->staged) * static_cast<int64_t>(HW);
-                hipLaunchKernelGGL(mc::k_frames_decode, grid_for(total, 256, 16384), dim3(256), 0, ctx->copy, total, H, W,
-                                   1, 1, ctx->d_in_raw.as<unsigned short>() + static_cast<size_t>(up->staged) * HW,
-                                   up->raw_scale, static_cast<const unsigned char *>(nullptr),
-                                   static_cast<const int *>(nullptr), static_cast<const int *>(nullptr),
-                                   ctx->d_in_depth.as<float>() + static_cast<size_t>(up->staged) * HW,
-                                   static_cast<unsigned char *>(nullptr));
-                MC_HIP(hipGetLastError());
-            } else {
-                stage_frames(ctx, up->depth, HW * 4, up->staged, f_hi, static_cast<char *>(ctx->d_in_depth.ptr), ctx->copy);
-            }
-            stage_frames(ctx, up->seg, HW, up->staged, f_hi, static_cast<char *>(ctx->d_in_seg.ptr), ctx->copy);
-            MC_HIP(hipEventRecord(ctx->ev_up, ctx->copy));
-            up->staged = f_hi;
-        };
-        // mask-pixel capacity for a batch of FB frames at the expected share (+ 1/16 and a frame's worth)
-        auto mask_cap = [&](double frac) {
-            const double fpx = static_cast<double>(FB) * static_cast<double>(HW);
-            return static_cast<size_t>(std::min(fpx, frac * fpx * 1.0625 + static_cast<double>(HW))) + 1024;
-        };
-        bp_reserve(ctx, FB, H, W, nbands, mask_cap(mfrac), s);
-        double mfrac_seen = 0.0;
-        const int PW = static_cast<int>((ctx->P_scene + 63) / 64) + 1;
-        const int qgrid = ctx->num_cu * 6;  // one bitmap per query workgroup (its largest grid)
-        if (ctx->d_bpbm.bytes < static_cast<size_t>(qgrid) * PW * 8) {
-            ctx->d_bpbm.reserve(static_cast<size_t>(qgrid) * PW * 8);
-            MC_HIP(hipMemsetAsync(ctx->d_bpbm.ptr, 0, ctx->d_bpbm.bytes, s));  // kept zero by k_bp_query
-            ctx->bp_bm_blocks = qgrid;
-        }
-        size_t tmp_cap = std::max<size_t>(ctx->d_tmp.bytes / 4, std::max<size_t>(1 << 20, ctx->bp_px_cap));
-        ctx->d_tmp.reserve(tmp_cap * 4);
-
-        mc::BpDev dv;
-        dv.trunc = prm.depth_trunc;
-        dv.vs = prm.voxel_size;
-        dv.rvs = 1.0 / prm.voxel_size;  // (IEEE division on the host: RN(1 / vs), div_rn's reciprocal)
-        dv.eps2 = prm.dbscan_eps * prm.dbscan_eps;
-        // k-NN pre-selection radii (fractions of eps, ascending, < 1): any choice gives the same
-        // results (the smallest radius holding >= k kept points is used); MC_KNN_RADII="a,b,c" tunes
-        double kfr[3] = {0.6, 0.75, 0.9};
-        if (const char *e = getenv("MC_KNN_RADII")) {
-            double a[3];
-            if (sscanf(e, "%lf,%lf,%lf", &a[0], &a[1], &a[2]) == 3 && 0 < a[0] && a[0] < a[1] && a[1] < a[2] && a[2] < 1)
-                for (int i = 0; i < 3; i++) kfr[i] = a[i];
-        }
-        for (int i = 0; i < 3; i++) dv.knn_r2[i] = (kfr[i] * prm.dbscan_eps) * (kfr[i] * prm.dbscan_eps);
-        dv.ce = prm.dbscan_eps * 1.01;
-        dv.frac = prm.component_min_fraction;
-        dv.std_ratio = prm.sor_std_ratio;
-        dv.cov = prm.coverage_threshold;
-        dv.r2 = rf * rf;
-        dv.scene_inv = 1.0f / (2.0f * rf);
-        dv.minpts = prm.dbscan_min_points;
-        dv.knn = prm.sor_neighbors;
-        dv.kball = prm.ball_k;
-        dv.few = prm.few_points;
-        dv.H = H;
-        dv.W = W;
-        dv.nbands = nbands;
-        // the pixel kernels' uchar4 / float4 loads need aligned frames (a caller's tensor view may start
-        // at any element); every batch starts HW pixels further on, a multiple of 4 when W is
-        // test knob: eps lists read only up to MC_BP_NBCAP entries (the rest take the cell walks)
-        dv.nbcap = mc::kBpNbCap;
-        if (const char *e = getenv("MC_BP_NBCAP")) dv.nbcap = std::min(mc::kBpNbCap, std::max(1, atoi(e)));
-        dv.vec4 = (W % 4 == 0 && reinterpret_cast<uintptr_t>(dep) % 16 == 0 && reinterpret_cast<uintptr_t>(sg) % 4 == 0)
-                      ? 1 : 0;
-
-        int *st = ctx->d_bpstat.as<int>();
-        if (!ctx->h_bpstat) MC_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_bpstat), BS_COUNT * sizeof(int),
-                                                 hipHostMallocDefault));
-        int *const hs = ctx->h_bpstat;  // pinned
-        if (!ctx->ev_pack) MC_HIP(hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
-        // the host side of a batch (its masks and statistics appended from h_bppack) runs while the
-        // next batch computes: the batch's copy into h_bppack is stream-ordered before the next batch,
-        // whose own copy comes only after its statistics sync, i.e. after this unpack
-        struct PendingBatch {
-            bool valid = false;
-            int b0 = 0, Mb = 0, NS = 0, nnzb = 0;
-            int64_t nnz_base = 0;
-        } pend;
-        auto unpack = [&]() {
-            if (!pend.valid) return;
-            MC_HIP(hipEventSynchronize(ctx->ev_pack));
-            const int Mb = pend.Mb, NS = pend.NS, nnzb = pend.nnzb, bb = pend.b0;
-            const int *col = ctx->h_bppack, *lab = col + Mb, *off = lab + Mb;
-            const int *sf = off + Mb, *sid = sf + NS, *snp = sid + NS, *snv = snp + NS, *sm = snv + NS,
-                      *sns = sm + NS, *scov = sns + NS, *snn = scov + NS;
-            for (int g = 0; g < Mb; g++) {
-                ctx->bp_col.push_back(bb + col[g]);
-                ctx->bp_label.push_back(lab[g]);
-            }
-            for (int g = 0; g < Mb; g++) ctx->bp_off.push_back(pend.nnz_base + (g + 1 < Mb ? off[g + 1] : nnzb));
-            for (int x = 0; x < NS; x++) {
-                const int kept = snn[x] >= 0;
-                const int row[MC_BP_NSTAT] = {bb + sf[x], sid[x], snp[x], snv[x], sm[x], sns[x], -1,
-                                              sns[x] >= prm.few_points ? scov[x] : 0, kept ? snn[x] : 0, kept};
-                ctx->bp_stats.insert(ctx->bp_stats.end(), row, row + MC_BP_NSTAT);
-            }
-            pend.valid = false;
-        };
-        for (int b0 = 0; b0 < F;) {
-            const int fb = std::min(FB, F - b0);
-            if (up) {
-                upload_to(b0 + fb);
-                MC_HIP(hipStreamWaitEvent(s, ctx->ev_up, 0));
-            }
-            const float *dB = dep + b0 * HW;
-            const uint8_t *sB = sg + b0 * HW;
-            const double *KB = Kp + 4 * static_cast<size_t>(b0), *TB = Tp + 16 * static_cast<size_t>(b0);
-            const int nslot = fb * 256;
-            {
-                TimedScope ts(ctx->timer, s, "bp_pixels");
-                hipLaunchKernelGGL(mc::k_bp_stat_init, dim3(1), dim3(64), 0, s, st, static_cast<int>(BS_COUNT));
-                MC_HIP(hipMemsetAsync(ctx->d_present.ptr, 0, fb * 8 * 4, s));
-                MC_HIP(hipMemsetAsync(ctx->d_fflags.ptr, 0, fb * 4, s));
-                hipLaunchKernelGGL(mc::k_bp_count, dim3(nbands, fb), dim3(256), 0, s, dB, sB, TB, dv,
-                                   ctx->d_band.as<int>(), ctx->d_present.as<unsigned>(), ctx->d_fflags.as<int>(),
-                                   ctx->d_bpvid.as<unsigned char>());
-                hipLaunchKernelGGL(mc::k_bp_frames, dim3(fb), dim3(1024), 0, s, ctx->d_band.as<int>(),
-                                   ctx->d_present.as<unsigned>(), ctx->d_fflags.as<int>(), dv, ctx->d_cand.as<int>(),
-                                   ctx->d_npix.as<int>(), st + BS_ERRF);
-                mc::scan_device_multi(s, nullptr, nslot, ctx->d_scanm.as<int>(), ctx->d_cand.as<int>(),
-                                      ctx->d_csidx.as<int>(), st + BS_NS, ctx->d_npix.as<int>(), ctx->d_poff.as<int>(),
-                                      st + BS_NPX);
-                hipLaunchKernelGGL(mc::k_bp_slots, grid_for(nslot), dim3(256), 0, s, ctx->d_cand.as<int>(),
-                                   ctx->d_csidx.as<int>(), ctx->d_npix.as<int>(), ctx->d_poff.as<int>(), nslot,
-                                   ctx->d_slot_of.as<int>(), ctx->d_slot_frame.as<int>(), ctx->d_slot_id.as<int>(),
-                                   ctx->d_slot_np.as<int>(), ctx->d_slot_pix.as<int>(), st + BS_NPX,
-                                   static_cast<int>(std::min<size_t>(ctx->bp_px_cap, INT_MAX)), st + BS_NS, st + BS_PXOVF);
-                hipLaunchKernelGGL(mc::k_bp_compact, dim3(nbands, fb), dim3(256), 0, s, ctx->d_bpvid.as<unsigned char>(),
-                                   ctx->d_band.as<int>(),
-                                   ctx->d_slot_of.as<int>(), ctx->d_slot_pix.as<int>(), dv,
-                                   ctx->d_pix_list.as<unsigned>());
-                bp_debug_sync(s, "bp_pixels");
-            }
-            {
-                TimedScope ts(ctx->timer, s, "bp_voxel");
-                hipLaunchKernelGGL(mc::k_bp_vox_order, dim3(1), dim3(1024), 0, s, st + BS_NS, ctx->d_slot_np.as<int>(),
-                                   ctx->d_vox_order.as<int>());
-                int *fb1 = ctx->d_vx_fb.as<int>(), *fb2 = fb1 + slots_cap(FB);
-                auto tier1 = [&](auto kern, int wg_per_cu) {
-                    hipLaunchKernelGGL(kern, dim3(ctx->num_cu * wg_per_cu), dim3(mc::kVxT), 0, s,
-                                       st + BS_NS, ctx->d_vox_order.as<int>(), ctx->d_slot_frame.as<int>(),
-                                       ctx->d_slot_np.as<int>(), ctx->d_slot_pix.as<int>(), ctx->d_pix_list.as<unsigned>(), dB,
-                                       KB, TB, dv, ctx->d_vx_pvid.as<int>(), ctx->d_vpts.as<double>(),
-                                       ctx->d_slot_nv.as<int>(), fb1, st + BS_VXFB, vx_global >= 1 ? 1 : 0,
-                                       ctx->d_slot_grid.as<double>());
-                };
-                auto tier2 = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(ctx->num_cu), dim3(mc::kVxT2), 0, s,
-                                       st + BS_VXFB, fb1, ctx->d_slot_frame.as<int>(), ctx->d_slot_np.as<int>(),
-                                       ctx->d_slot_pix.as<int>(), ctx->d_pix_list.as<unsigned>(), dB, KB, TB, dv,
-                                       ctx->d_vx_pvid.as<int>(), ctx->d_vpts.as<double>(), ctx->d_slot_nv.as<int>(), fb2,
-                                       st + BS_VXFB2, vx_global == 1 ? 1 : 0, ctx->d_slot_grid.as<double>());
-                };
-                // five workgroups per CU (32 KB of LDS, <= 96 VGPRs each) for the first tier
-                tier1(mc::k_bp_voxel_lds<mc::kVxT, mc::kVxH, mc::kVxV, 0, mc::kVxWpe>, mc::kVxWpe);
-                tier2(mc::k_bp_voxel_lds<mc::kVxT2, mc::kVxH2, mc::kVxV2, mc::kVxL2>);
-                hipLaunchKernelGGL(mc::k_bp_voxel, dim3(ctx->num_cu), dim3(256), 0, s, st + BS_VXFB2,
-                                   fb2, ctx->d_slot_frame.as<int>(), ctx->d_slot_np.as<int>(),
-                                   ctx->d_slot_pix.as<int>(), ctx->d_pix_list.as<unsigned>(), dB, KB, TB, dv,
-                                   ctx->d_hkey.as<unsigned long long>(), ctx->d_hvid.as<int>(), ctx->d_hfirst.as<int>(),
-                                   ctx->d_vox_entry.as<int>(), ctx->d_acc.as<double>(), ctx->d_vpts.as<double>(),
-                                   ctx->d_slot_nv.as<int>(), st + BS_VOXERR, ctx->d_slot_grid.as<double>());
-                bp_debug_sync(s, "bp_voxel");
-            }
-            {
-                TimedScope ts(ctx->timer, s, "bp_denoise");
-                const int ncap = static_cast<int>(slots_cap(fb));
-                // largest first again, now by voxel count (the denoise's and the query's cost)
-                hipLaunchKernelGGL(mc::k_bp_vox_order, dim3(1), dim3(1024), 0, s, st + BS_NS, ctx->d_slot_nv.as<int>(),
-                                   ctx->d_vox_order.as<int>());
-                hipLaunchKernelGGL(mc::k_bp_classify, dim3(64), dim3(256), 0, s, st + BS_NS, ctx->d_slot_nv.as<int>(),
-                                   ctx->d_vox_order.as<int>(), ncap, min_cls, st + BS_CLS, ctx->d_cls_list.as<int>());
-                // the few slots beyond the LDS classes run on the side stream, beside the classes
-                MC_HIP(hipEventRecord(ctx->ev_fork, s));
-                MC_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-                bp_denoise_class<16384>(ctx, ctx->side, 5, ncap, st, dv);  // few, large slots
-                hipLaunchKernelGGL(mc::k_bp_denoise, dim3(ctx->num_cu), dim3(256), 0, ctx->side, st + BS_CLS + mc::kBpClasses,
-                                   ctx->d_cls_list.as<int>() + mc::kBpClasses * static_cast<size_t>(ncap), ctx->d_slot_pix.as<int>(), ctx->d_slot_nv.as<int>(), dv, ctx->d_vpts.as<double>(),
-                                   ctx->d_pcell.as<unsigned long long>(), ctx->d_pbkt.as<int>(), ctx->d_bcnt.as<int>(),
-                                   ctx->d_bstart.as<int>(), ctx->d_blist.as<int>(), ctx->d_ncnt.as<int>(),
-                                   ctx->d_par.as<int>(), ctx->d_droot.as<int>(), ctx->d_rnk.as<int>(),
-                                   ctx->d_lab.as<int>(), ctx->d_ccnt.as<int>(), ctx->d_ssidx.as<int>(),
-                                   ctx->d_avg.as<double>(), ctx->d_qpts.as<float>(), ctx->d_slot_m.as<int>(),
-                                   ctx->d_slot_ns.as<int>(), ctx->d_slot_box.as<float>());
-                MC_HIP(hipEventRecord(ctx->ev_join, ctx->side));
-                // the LDS classes side by side, each on its own stream: a class with few slots
-                // (the large ones) leaves most CUs to the others instead of serialising the batch
-                for (int c = 0; c < mc::kBpStreamClasses; c++) MC_HIP(hipStreamWaitEvent(ctx->cls_stream[c], ctx->ev_fork, 0));
-                bp_denoise_class<3072>(ctx, ctx->cls_stream[3], 3, ncap, st, dv);
-                bp_denoise_class<4096>(ctx, ctx->cls_stream[4], 4, ncap, st, dv);
-                bp_denoise_class<2048>(ctx, ctx->cls_stream[2], 2, ncap, st, dv);
-                bp_denoise_class<1024>(ctx, ctx->cls_stream[1], 1, ncap, st, dv);
-                bp_denoise_class<512>(ctx, ctx->cls_stream[0], 0, ncap, st, dv);
-                for (int c = 0; c < mc::kBpStreamClasses; c++) {
-                    MC_HIP(hipEventRecord(ctx->ev_cls[c], ctx->cls_stream[c]));
-                    MC_HIP(hipStreamWaitEvent(s, ctx->ev_cls[c], 0));
-                }
-                MC_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));
-                // the deferred points' ring search, then every LDS-class slot's statistics and survivors
-                bp_denoise_tail_launch(ctx, s, ncap, st, dv);
-                bp_debug_sync(s, "bp_denoise");
-            }
-            {
-                TimedScope ts(ctx->timer, s, "bp_query");
-                auto query = [&](auto kern, int grid) {
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, st + BS_NS,
-                                   ctx->d_slot_pix.as<int>(), ctx->d_slot_ns.as<int>(), ctx->d_slot_box.as<float>(),
-                                   ctx->d_qpts.as<float>(), dv, ctx->d_gpts.as<float4>(), ctx->d_gidx.as<int>(),
-                                   ctx->d_gcell.as<unsigned long long>(), ctx->d_gstart.as<int>(), ctx->gnb,
-                                   ctx->d_bpbm.as<unsigned long long>(), PW, ctx->d_tmp.as<int>(),
-                                   static_cast<int>(std::min<size_t>(tmp_cap, INT_MAX)), st + BS_TOP,
-                                   ctx->d_slot_nn.as<int>(), ctx->d_slot_toff.as<int>(), ctx->d_slot_cov.as<int>(),
-                                   st + BS_OVF, ctx->d_vox_order.as<int>());
-                };
-                // the query waits on dependent cell-range and point loads: as many waves as the
-                // registers allow (the 20-entry best list of ball_k <= 20: 76 VGPRs, six workgroups per
-                // CU, C3 query 8.4 -> 6.5 ms per scene; 32 entries: 89 VGPRs, five)
-                if (prm.ball_k <= 20) query(mc::k_bp_query<1, 20>, ctx->num_cu * 6);
-                else query(mc::k_bp_query<1, mc::kBpBallMax>, ctx->num_cu * 5);
-                bp_debug_sync(s, "k_bp_query");
-                hipLaunchKernelGGL(mc::k_bp_keepflags, grid_for(nslot), dim3(256), 0, s, st + BS_NS,
-                                   ctx->d_slot_nn.as<int>(), ctx->d_kflag.as<int>(), ctx->d_ksize.as<int>());
-                mc::scan_device_multi(s, st + BS_NS, nslot, ctx->d_scanm.as<int>(), ctx->d_kflag.as<int>(),
-                                      ctx->d_midx.as<int>(), st + BS_M, ctx->d_ksize.as<int>(), ctx->d_moff.as<int>(),
-                                      st + BS_NNZ);
-                bp_debug_sync(s, "bp_query");
-            }
-            MC_HIP(hipMemcpyAsync(hs, st, BS_COUNT * 4, hipMemcpyDeviceToHost, s));
-            upload_to(std::min(F, b0 + fb + FB));  // the host copies the next batch while this one computes
-            unpack();                               // and appends the previous batch's results
-            MC_HIP(hipStreamSynchronize(s));
-            ctx->timer.collect();
-            if (hs[BS_ERRF] != INT_MAX) {
-                ctx->bp_err_frame = b0 + hs[BS_ERRF];
-                throw McError{MC_ERR_INVALID, "frame " + std::to_string(b0 + hs[BS_ERRF]) +
-                                                  ": depth pixel equal to depth_trunc (the reference raises "
-                                                  "IndexError at utils/mask_backprojection.py:100)"};
-            }
-            MC_REQUIRE(!(hs[BS_VOXERR] & 2), MC_ERR_HIP, "voxel hash table not empty at slot start (internal error)");
-            MC_REQUIRE(hs[BS_DNERR] == 0, MC_ERR_HIP,
-                       "denoise: k-NN ring-search queue " + std::string(hs[BS_DNERR] & 1 ? "entry" : "region") +
-                           " out of range (internal error)");
-            MC_REQUIRE(hs[BS_VOXERR] == 0, MC_ERR_UNSUPPORTED, "voxel index beyond 2^21 per axis");
-            if (hs[BS_PXOVF]) {  // more mask pixels than the capacity (nothing past the pixel lists ran): grow, redo
-                const double frac = static_cast<double>(hs[BS_NPX]) / (static_cast<double>(fb) * HW);
-                ctx->bp_mfrac = std::max(ctx->bp_mfrac, frac);
-                // within the byte budget: at the observed share the batch takes fewer frames (a denser
-                // scene than the share learned so far), instead of arrays up to 1 / share times the budget
-                const int fb_was = FB;
-                if (!fixed_batch) {
-                    const double per_px = static_cast<double>(kBpBytesPerFramePixel) +
-                                          std::min(1.0, frac * 1.0625 + 1.0 / FB) * kBpBytesPerMaskPixel;
-                    const double fit = std::floor(static_cast<double>(bud_bytes) / (per_px * static_cast<double>(HW)));
-                    FB = std::max(1, std::min(FB, static_cast<int>(std::min(fit, 1e9))));
-                }
-                // the same frames again: room for every pixel they listed; fewer frames: the share's room
-                // (another overflow shrinks the batch or grows the arrays again, so the redo terminates)
-                bp_reserve(ctx, FB, H, W, nbands,
-                           FB < fb_was ? mask_cap(frac) : std::max(mask_cap(frac), static_cast<size_t>(hs[BS_NPX]) + 1024), s);
-                ctx->bp_redo++;
-                continue;
-            }
-            mfrac_seen = std::max(mfrac_seen, static_cast<double>(hs[BS_NPX]) / (static_cast<double>(fb) * HW));
-            if (hs[BS_OVF]) {  // neighbour sets overflowed tmp: grow and redo the batch
-                tmp_cap = static_cast<size_t>(hs[BS_TOP]) + (static_cast<size_t>(hs[BS_TOP]) >> 1) + 1024;
-                ctx->d_tmp.reserve(tmp_cap * 4);
-                continue;
-            }
-            const int NS = hs[BS_NS], Mb = hs[BS_M], nnzb = hs[BS_NNZ];
-            ctx->d_out_col.reserve((Mb + 1) * 4);
-            ctx->d_out_label.reserve((Mb + 1) * 4);
-            ctx->d_out_off.reserve((Mb + 1) * 4);
-            grow_keep(ctx->d_bp_pts, (ctx->bp_nnz + nnzb + 1) * 4, ctx->bp_nnz * 4, s);
-            {
-                TimedScope ts(ctx->timer, s, "bp_query");
-                hipLaunchKernelGGL(mc::k_bp_emit, grid_for(std::max(NS, 1), 4, 4096), dim3(256), 0, s, st + BS_NS,
-                                   ctx->d_slot_frame.as<int>(), ctx->d_slot_id.as<int>(), ctx->d_slot_nn.as<int>(),
-                                   ctx->d_slot_toff.as<int>(), ctx->d_midx.as<int>(), ctx->d_moff.as<int>(),
-                                   ctx->d_tmp.as<int>(), ctx->d_out_col.as<int>(), ctx->d_out_label.as<int>(),
-                                   ctx->d_out_off.as<int>(), ctx->d_bp_pts.as<int>() + ctx->bp_nnz);
-            }
-            // the kept masks' (col, label, off) and the 8 per-candidate statistics arrays: packed on
-            // the device, one copy into pinned memory
-            const size_t npack = 3 * static_cast<size_t>(Mb) + 8 * static_cast<size_t>(NS);
-            ctx->d_bppack.reserve((npack + 1) * 4);
-            if (ctx->h_bppack_n < npack) {
-                if (ctx->h_bppack) MC_HIP(hipHostFree(ctx->h_bppack));
-                ctx->h_bppack = nullptr;
-                ctx->h_bppack_n = 0;
-                const size_t n = npack + npack / 2 + 1024;
-                MC_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_bppack), n * 4, hipHostMallocDefault));
-                ctx->h_bppack_n = n;
-            }
-            if (npack) {
-                hipLaunchKernelGGL(mc::k_bp_pack, grid_for(static_cast<int64_t>(npack)), dim3(256), 0, s, st + BS_NS, st + BS_M,
-                                   ctx->d_out_col.as<int>(), ctx->d_out_label.as<int>(), ctx->d_out_off.as<int>(),
-                                   ctx->d_slot_frame.as<int>(), ctx->d_slot_id.as<int>(), ctx->d_slot_np.as<int>(),
-                                   ctx->d_slot_nv.as<int>(), ctx->d_slot_m.as<int>(), ctx->d_slot_ns.as<int>(),
-                                   ctx->d_slot_cov.as<int>(), ctx->d_slot_nn.as<int>(), ctx->d_bppack.as<int>());
-                MC_HIP(hipMemcpyAsync(ctx->h_bppack, ctx->d_bppack.ptr, npack * 4, hipMemcpyDeviceToHost, s));
-            }
-            MC_HIP(hipEventRecord(ctx->ev_pack, s));
-            bp_debug_sync(s, "bp_emit");
-            pend.valid = true;
-            pend.b0 = b0;
-            pend.Mb = Mb;
-            pend.NS = NS;
-            pend.nnzb = nnzb;
-            pend.nnz_base = ctx->bp_nnz;
-            ctx->bp_nnz += nnzb;
-            b0 += fb;
-        }
-        // the next call's batches are sized for the share seen, decaying from the larger of earlier calls
-        // (a stream of scenes on one context: a sparse scene does not at once size batches a denser one
-        // after it overflows)
-        if (mfrac_seen > 0.0) {
-            ctx->bp_mfrac = ctx->bp_mfrac_obs ? std::max(mfrac_seen, 0.5 * (ctx->bp_mfrac + mfrac_seen)) : mfrac_seen;
-            ctx->bp_mfrac_obs = true;
-        }
-        ctx->bp_last_fb = FB;
-        unpack();
-        MC_HIP(hipStreamSynchronize(s));
-        ctx->have_bp = true;
-    });
-}
-
-int mc_backproject_get_info(mc_ctx *ctx, mc_bp_info *info)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(info, MC_ERR_INVALID, "null info");
-        info->num_frames = ctx->bp_F;
-        info->num_candidates = static_cast<int32_t>(ctx->bp_stats.size() / MC_BP_NSTAT);
-        info->num_masks = static_cast<int32_t>(ctx->bp_col.size());
-        info->error_frame = ctx->bp_err_frame;
-        info->num_mask_points = ctx->bp_nnz;
-    });
-}
-
-int mc_backproject_get_batching(mc_ctx *ctx, int64_t *out4)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(out4, MC_ERR_INVALID, "null output");
-        out4[0] = ctx->bp_last_fb;
-        out4[1] = static_cast<int64_t>(ctx->bp_px_cap);
-        out4[2] = static_cast<int64_t>(ctx->bp_px_cap * kBpBytesPerMaskPixel + ctx->bp_fpx_cap * kBpBytesPerFramePixel);
-        out4[3] = ctx->bp_redo;
-    });
-}
-
-int mc_backproject_get_masks(mc_ctx *ctx, int32_t *mask_col, int32_t *mask_label, int64_t *mask_off,
-                             int32_t *mask_pts)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_bp, MC_ERR_STATE, "no back-projection result");
-        const size_t M = ctx->bp_col.size();
-        if (mask_col) std::copy(ctx->bp_col.begin(), ctx->bp_col.end(), mask_col);
-        if (mask_label) std::copy(ctx->bp_label.begin(), ctx->bp_label.end(), mask_label);
-        if (mask_off) std::copy(ctx->bp_off.begin(), ctx->bp_off.begin() + M + 1, mask_off);
-        if (mask_pts && ctx->bp_nnz)
-            MC_HIP(hipMemcpyAsync(mask_pts, ctx->d_bp_pts.ptr, ctx->bp_nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
-        MC_HIP(hipStreamSynchronize(ctx->stream));
-    });
-}
-
-int mc_backproject_copy_points_device(mc_ctx *ctx, int32_t *mask_pts_dev)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_bp, MC_ERR_STATE, "no back-projection result");
-        MC_REQUIRE(mask_pts_dev || !ctx->bp_nnz, MC_ERR_INVALID, "null destination");
-        if (ctx->bp_nnz)
-            MC_HIP(hipMemcpyAsync(mask_pts_dev, ctx->d_bp_pts.ptr, ctx->bp_nnz * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    });
-}
-
-int mc_backproject_get_candidates(mc_ctx *ctx, int32_t *stats)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_bp, MC_ERR_STATE, "no back-projection result");
-        std::copy(ctx->bp_stats.begin(), ctx->bp_stats.end(), stats);
-    });
-}
-
-#ifdef MC_BP_STAMPS
-// diagnostic builds only: read (and clear) k_bp_denoise's per-step clock totals
-int mc_debug_bp_slot_times(unsigned *out, int n)
-{
-    n = std::min(n, 1 << 16);
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(mc::g_bp_slot_time), n * 4) == hipSuccess ? MC_OK : MC_ERR_HIP;
-}
-int mc_debug_bp_stamps(unsigned long long *out32)
-{
-    if (hipMemcpyFromSymbol(out32, HIP_SYMBOL(mc::g_bp_stamps), 48 * 8) != hipSuccess) return MC_ERR_HIP;
-    static const unsigned long long zero[48] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(mc::g_bp_stamps), zero, 48 * 8) == hipSuccess ? MC_OK : MC_ERR_HIP;
-}
-#endif
-
-int mc_scene_use_backprojection(mc_ctx *ctx)
-{
-    if (!ctx) return MC_ERR_INVALID;
-    if (!ctx->have_bp) {
-        ctx->err = "no back-projection result";
-        return MC_ERR_STATE;
-    }
-    const std::vector<int32_t> col = ctx->bp_col, lab = ctx->bp_label;
-    const std::vector<int64_t> off = ctx->bp_off;
-    return mc_scene_set_masks(ctx, ctx->P_scene, ctx->bp_F, static_cast<int32_t>(col.size()), col.data(), lab.data(),
-                              off.data(), ctx->d_bp_pts.as<int32_t>(), 1);
-}
-
+#include "mc_bp_host.inl"
 
 // ---------------------------------------------------------------------------------------------
 // post-processing (utils/post_process.py:173-194)
 // ---------------------------------------------------------------------------------------------
-}  // extern "C"
 
 namespace {
 
@@ -3169,7 +2235,7 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
         MC_REQUIRE(ctx->have_cluster, MC_ERR_STATE, "no clustering result (mc_cluster_run first)");
         MC_REQUIRE(ctx->nodes_from_graph, MC_ERR_STATE, "the nodes were given by mc_nodes_set: no mask table");
         MC_REQUIRE(!sharded(ctx) || ctx->sh_pending == 0, MC_ERR_STATE, "this rank does not hold the full result");
-        MC_REQUIRE(scene_xyz || (ctx->have_points && ctx->P_scene == ctx->P), MC_ERR_STATE,
+        MC_REQUIRE(scene_xyz || (ctx->bp.have_points && ctx->bp.P == ctx->P), MC_ERR_STATE,
                    "no scene points: pass scene_xyz or call mc_scene_set_points");
         sync_stats(ctx);
         hipStream_t s = ctx->stream;
@@ -3181,7 +2247,7 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
             mc::TimedScope ts(ctx->timer, s, "pp_prep");
             if (!scene_xyz) {  // the float32 points, widened exactly
                 scene.reserve(static_cast<size_t>(P) * 24 + 8);
-                hipLaunchKernelGGL(mc::k_pp_widen, grid_for(3 * P), dim3(256), 0, s, ctx->d_scene.as<float>(), 3 * P,
+                hipLaunchKernelGGL(mc::k_pp_widen, grid_for(3 * P), dim3(256), 0, s, ctx->bp.scene.as<float>(), 3 * P,
                                    scene.as<double>());
                 d_scene = scene.as<double>();
             } else if (!scene_on_device) {
@@ -3522,7 +2588,7 @@ int mc_bits_unpack(const uint64_t *words, int64_t rows, int32_t words_per_row, i
     const int64_t bytes = rows * ncols;
     int nt = static_cast<int>(std::min<int64_t>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())),
                                                 std::max<int64_t>(1, bytes >> 22)));
-    if (const char *e = getenv("MC_STAGE_THREADS")) nt = std::max(1, std::min(64, atoi(e)));
+    nt = stage_threads_knob(nt);
     if (nt <= 1) {
         work(0, rows);
         return MC_OK;

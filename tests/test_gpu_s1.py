@@ -16,6 +16,17 @@ pytestmark = pytest.mark.gpu
 CMP_COLS = [(1, 0), (2, 1), (3, 2), (4, 3), (5, 4), (7, 6), (8, 7), (9, 8)]
 
 
+def _plan_constant(name):
+    """a byte constant of the batch plan (maskclustering_amd/csrc/mc_bp_plan.hpp)"""
+    import re
+    hpp = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "maskclustering_amd", "csrc",
+                       "mc_bp_plan.hpp")
+    return int(re.search(rf"constexpr size_t {name} = (\d+);", open(hpp).read()).group(1))
+
+
+MASK_PX_BYTES = _plan_constant("kBpBytesPerMaskPixel")  # HBM of the per-batch arrays per mask pixel
+
+
 @pytest.fixture(scope="module")
 def ctx():
     from maskclustering_amd import _native
@@ -218,6 +229,39 @@ def _check_dense(ctx):
     _check_against_oracle(ctx, make_frames_shape("tiny", seed=5, H=360, W=480, num_frames=3))
 
 
+def test_zero_frames(ctx):
+    """No frames, through the contiguous entry ([0, 48, 64] arrays) and through mc_backproject_frames
+    (num_frames = 0, null arrays): MC_OK and an empty result, and the context then runs s1_tiny to
+    the golden output."""
+    from maskclustering_amd import _native
+    z = dict(np.load(os.path.join(GOLDEN, "s1_tiny.npz")))
+    ctx.set_points(np.asarray(z["in_scene"], np.float64).astype(np.float32))
+
+    def check_empty():
+        info = ctx.bp_info()
+        assert (info.num_frames, info.num_masks, info.num_candidates, info.num_mask_points) == (0, 0, 0, 0)
+        col, lab, off, pts = ctx.bp_masks()
+        assert len(col) == 0 and len(lab) == 0 and len(pts) == 0
+        np.testing.assert_array_equal(off, [0])
+        assert len(ctx.bp_candidates()) == 0
+
+    ctx.backproject(np.zeros((0, 48, 64), np.float32), np.zeros((0, 48, 64), np.uint8), np.zeros((0, 4)),
+                    np.zeros((0, 4, 4)))
+    check_empty()
+    _check_golden(ctx, "s1_tiny")
+    assert ctx.bp_info().num_masks > 0
+    assert ctx.L.mc_backproject_frames(ctx.h, 0, 48, 64, None, None, None, None, None) == _native.MC_OK
+    check_empty()
+    _check_golden(ctx, "s1_tiny")
+
+
+@pytest.mark.parametrize("tail_wg", ["0", "-3"])
+def test_tail_workgroups_knob_is_clamped(ctx, monkeypatch, tail_wg):
+    """MC_BP_TAILWG below 1 (an empty k_bp_denoise_tail grid) is clamped to 1: the golden output."""
+    monkeypatch.setenv("MC_BP_TAILWG", tail_wg)
+    _check_golden(ctx, "s1_tiny")
+
+
 @pytest.mark.parametrize("min_cls", [1, 2, 3, 4, 5, 6])
 def test_denoise_size_classes_match_oracle(ctx, monkeypatch, min_cls):
     """Every denoise size class (LDS 512/1024/2048 points, the lean 3072- and 4096-point classes,
@@ -394,8 +438,8 @@ def test_denser_scene_after_sparse_one_stays_within_budget():
     valid = (fr.depth > 0) & (fr.depth <= 20)
     dense_px = int(((fr.seg != 0) & valid).sum())
     sparse_px = int(((sparse != 0) & valid).sum())
-    budget = max(int(0.5 * dense_px * 196), 250 * HW)
-    assert dense_px * 196 > budget and sparse_px * 196 * 4 < budget   # the case the redo must bound
+    budget = max(int(0.5 * dense_px * MASK_PX_BYTES), 250 * HW)
+    assert dense_px * MASK_PX_BYTES > budget and sparse_px * MASK_PX_BYTES * 4 < budget   # the case the redo must bound
     ref = _native.Context(0)
     want_sparse = _run(ref, fr.scene_points, fr.depth, sparse, fr.intrinsics, fr.poses)
     want_dense = _run(ref, fr.scene_points, fr.depth, fr.seg, fr.intrinsics, fr.poses)
@@ -411,4 +455,4 @@ def test_denser_scene_after_sparse_one_stays_within_budget():
         np.testing.assert_array_equal(x, y)
     assert after["redone"] > before["redone"], (before, after)
     assert after["frames_per_batch"] < F, after
-    assert after["bytes_held"] <= budget + 196 * HW + 4 * F * HW + 196 * 2048, (budget, after)
+    assert after["bytes_held"] <= budget + MASK_PX_BYTES * HW + 4 * F * HW + MASK_PX_BYTES * 2048, (budget, after)
