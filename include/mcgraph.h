@@ -371,6 +371,60 @@ int mc_eval_match_counts(mc_ctx *ctx, int64_t num_points, int32_t num_pred, cons
                          int64_t *pred_verts /* K */, int64_t *void_intersection /* K */,
                          int64_t *intersection /* K*num_gt */);
 
+/* ---- AP evaluation over accumulated scans ------------------------------
+ * Replaces evaluation/evaluate.py:254-329 on point lists (no [P, K] prediction matrix, no
+ * [K, G] intersection matrix) and :53-205 (evaluate_matches): AP per (class, overlap) over every
+ * scan added since mc_ev_begin, equal to the reference's up to the summation order of its final
+ * dot product.  The state lives in the context.
+ *
+ * mc_ev_begin starts or resets an accumulation: the class table (ids in [0, 2e6), distinct), the
+ * overlap thresholds as the doubles the caller computed (at most 32), min_region_size, no_class
+ * (every ground-truth id becomes id % 1000 + class_ids[0] * 1000 and every prediction has class
+ * class_ids[0]).
+ *
+ * A scan's tables (mc_ev_scan_info / mc_ev_get_scan return the last added scan's):
+ *   ground truth  class index, instance id, vert_count: the distinct non-zero ids whose
+ *                 id / 1000 is a class id, grouped by class in the table's order, ascending id
+ *   predictions   class index, vert_count, void_intersection, score: the kept predictions
+ *                 (class in the table, at least min_region_size points) in input order
+ *   pairs         (prediction, ground truth, intersection): the non-zero intersections of a
+ *                 prediction with the instances of its own class, sorted by (prediction, ground truth)
+ *
+ * mc_ev_add_scan: gt_ids [num_points] (label * 1000 + k, 0 = none) and the predictions as point
+ * lists in CSR form (what mc_pp_export fills; ids within a list distinct), host arrays or, with
+ * on_device, device pointers.  pred_classes NULL: class id 0; pred_scores NULL: 1.0.  The range
+ * checks (point ids in [0, num_points), gt_ids >= 0, offsets from 0 ascending to num_pred_pts)
+ * run in a kernel behind one flag the host reads once; the host does O(instances + predictions
+ * + pairs) work.  MC_ERR_INVALID leaves the accumulation as it was.
+ * mc_ev_add_scan_clustered: the predictions are the final objects of the context's last
+ * mc_pp_run* (class id 0, score 1.0, as export_class_agnostic_mask writes them); MC_ERR_STATE
+ * without a post-processing result.
+ * mc_ev_add_matches: a scan given as its tables (host arrays).  Ground truths must be grouped by
+ * ascending class index; a ground truth's matched predictions are taken in the pair list's order.
+ *
+ * mc_ev_ap: ap [C * O] (NaN without ground truth, 0 with ground truth but no prediction or no
+ * example) and stats [C * O * 4]: examples, true examples, hard false negatives,
+ * has_gt | has_pred << 1.  May be called again as scans are added.
+ * mc_ev_get_curve: the cell's distinct scores ascending with their (tp, fp, fn); num_scores is
+ * always set (0 for a cell without a curve), the arrays may be NULL for the size query. */
+int mc_ev_begin(mc_ctx *ctx, int32_t num_classes, const int32_t *class_ids, int32_t num_overlaps, const double *overlaps,
+                int64_t min_region_size, int no_class);
+int mc_ev_add_scan(mc_ctx *ctx, int64_t num_points, const int32_t *gt_ids /* P */, int32_t num_pred,
+                   const int64_t *pred_off /* K+1 */, int64_t num_pred_pts, const int32_t *pred_pts,
+                   const int32_t *pred_classes /* K or NULL */, const double *pred_scores /* K or NULL */, int on_device);
+int mc_ev_add_scan_clustered(mc_ctx *ctx, const int32_t *gt_ids /* the scene's P */, int on_device);
+int mc_ev_add_matches(mc_ctx *ctx, int32_t num_gt, const int32_t *gt_class, const int32_t *gt_id, const int64_t *gt_vert,
+                      int32_t num_pred, const int32_t *pred_class, const int64_t *pred_vert, const int64_t *pred_void,
+                      const double *pred_score, int64_t num_pairs, const int32_t *pair_pred, const int32_t *pair_gt,
+                      const int64_t *pair_int);
+int mc_ev_scan_info(mc_ctx *ctx, int32_t *num_gt, int32_t *num_pred, int64_t *num_pairs);
+int mc_ev_get_scan(mc_ctx *ctx, int32_t *gt_class, int32_t *gt_id, int64_t *gt_vert, int32_t *pred_class,
+                   int64_t *pred_vert, int64_t *pred_void, double *pred_score, int32_t *pair_pred, int32_t *pair_gt,
+                   int64_t *pair_int);
+int mc_ev_ap(mc_ctx *ctx, double *ap /* C*O */, int64_t *stats /* C*O*4 */);
+int mc_ev_get_curve(mc_ctx *ctx, int32_t class_index, int32_t overlap_index, int64_t *num_scores, double *scores,
+                    int64_t *tp, int64_t *fp, int64_t *fn);
+
 /* ---- frame decode -------------------------------------------------------
  * Replaces the per-frame host work of dataset/scannet.py:49-54 (get_depth: uint16 / depth_scale
  * as float64, stored float32; matterport.py:92 and scannetpp.py:169 alike) and :68-73

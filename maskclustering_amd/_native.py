@@ -42,6 +42,8 @@ EXPORTED = [
     "mc_cluster_set_edge_capture", "mc_cluster_get_edges", "mc_openvoc_query", "mc_bits_unpack", "mc_setorder_replay",
     "mc_setorder_begin", "mc_setorder_finish", "mc_setorder_free",
     "mc_comm_unique_id", "mc_ctx_comm_init", "mc_ctx_attach_comm",
+    "mc_ev_begin", "mc_ev_add_scan", "mc_ev_add_scan_clustered", "mc_ev_add_matches", "mc_ev_scan_info", "mc_ev_get_scan",
+    "mc_ev_ap", "mc_ev_get_curve",
 ]
 MC_COMM_ID_BYTES = 128
 
@@ -196,6 +198,14 @@ def load():
         "mc_comm_unique_id": (ctypes.c_int, [vp]),
         "mc_ctx_comm_init": (ctypes.c_int, [vp, vp, i32, i32]),
         "mc_ctx_attach_comm": (ctypes.c_int, [vp, vp]),
+        "mc_ev_begin": (ctypes.c_int, [vp, i32, vp, i32, vp, i64, ctypes.c_int]),
+        "mc_ev_add_scan": (ctypes.c_int, [vp, i64, vp, i32, vp, i64, vp, vp, vp, ctypes.c_int]),
+        "mc_ev_add_scan_clustered": (ctypes.c_int, [vp, vp, ctypes.c_int]),
+        "mc_ev_add_matches": (ctypes.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp]),
+        "mc_ev_scan_info": (ctypes.c_int, [vp, P(i32), P(i32), P(i64)]),
+        "mc_ev_get_scan": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mc_ev_ap": (ctypes.c_int, [vp, vp, vp]),
+        "mc_ev_get_curve": (ctypes.c_int, [vp, i32, i32, P(i64), vp, vp, vp, vp]),
     }
     # MCGRAPH_LIB_PARTIAL=1 (A/B scripts only): an older variant library may lack newer entry points
     partial = os.environ.get("MCGRAPH_LIB_PARTIAL") == "1"
@@ -830,6 +840,106 @@ def _eval_methods():
 
 
 _eval_methods()
+
+
+EV_TABLE_KEYS = (("gt_cls", "int32"), ("gt_id", "int32"), ("gt_vert", "int64"), ("pr_cls", "int32"), ("pr_vert", "int64"),
+                 ("pr_void", "int64"), ("pr_score", "float64"), ("pair_pred", "int32"), ("pair_gt", "int32"),
+                 ("pair_int", "int64"))
+
+
+def _ev_methods():
+    def ev_begin(self, class_ids, overlaps=None, min_region_size=100, no_class=False):
+        """mc_ev_begin: start or reset the AP accumulation.  overlaps default to the reference's
+        (evaluate.py:44), passed as the doubles numpy computed."""
+        ids = np.ascontiguousarray(class_ids, np.int32)
+        ov = np.ascontiguousarray(np.append(np.arange(0.5, 0.95, 0.05), 0.25) if overlaps is None else overlaps, np.float64)
+        self._check(self.L.mc_ev_begin(self.h, len(ids), _ptr(ids), len(ov), _ptr(ov), int(min_region_size),
+                                       1 if no_class else 0))
+        self._ev_shape = (len(ids), len(ov))
+
+    def ev_add_scan(self, gt_ids, pred_off, pred_pts, pred_classes=None, pred_scores=None):
+        """mc_ev_add_scan: ground-truth ids [P] and predictions as point lists (CSR): numpy arrays, or
+        contiguous tensors on the context's device (int32 / int64 / float64 as in the header), all of one kind."""
+        dev = hasattr(gt_ids, "data_ptr")
+        if dev:
+            import torch
+            want = (torch.int32, torch.int64, torch.int32, torch.int32, torch.float64)
+            args = (gt_ids, pred_off, pred_pts, pred_classes, pred_scores)
+            for a, dt in zip(args, want):
+                if a is not None and (a.device.type != "cuda" or a.dtype != dt or not a.is_contiguous()):
+                    raise ValueError("ev_add_scan: device inputs must be contiguous tensors of the header's types")
+            p = [None if a is None else ctypes.c_void_p(a.data_ptr()) for a in args]
+            P, K, n = gt_ids.numel(), pred_off.numel() - 1, pred_pts.numel()
+        else:
+            args = (np.ascontiguousarray(gt_ids, np.int32), np.ascontiguousarray(pred_off, np.int64),
+                    np.ascontiguousarray(pred_pts, np.int32),
+                    None if pred_classes is None else np.ascontiguousarray(pred_classes, np.int32),
+                    None if pred_scores is None else np.ascontiguousarray(pred_scores, np.float64))
+            p = [_ptr(a) for a in args]
+            P, K, n = len(args[0]), len(args[1]) - 1, len(args[2])
+        if K < 0:
+            raise ValueError("ev_add_scan: pred_off needs at least one entry")
+        self._check(self.L.mc_ev_add_scan(self.h, P, p[0], K, p[1], n, p[2], p[3], p[4], 1 if dev else 0))
+
+    def ev_add_scan_clustered(self, gt_ids):
+        """mc_ev_add_scan_clustered: the last post-processing result's final objects against gt_ids [P]
+        (numpy, or an int32 tensor on the context's device)."""
+        if hasattr(gt_ids, "data_ptr"):
+            import torch
+            if gt_ids.device.type != "cuda" or gt_ids.dtype != torch.int32 or not gt_ids.is_contiguous():
+                raise ValueError("ev_add_scan_clustered: a device gt_ids must be a contiguous int32 tensor")
+            n, p, dev = gt_ids.numel(), ctypes.c_void_p(gt_ids.data_ptr()), 1
+        else:
+            keep = np.ascontiguousarray(gt_ids, np.int32)
+            n, p, dev = len(keep), _ptr(keep), 0
+        if getattr(self, "_pp_points", None) is not None and n != self._pp_points:
+            raise ValueError(f"ev_add_scan_clustered: {n} ground-truth ids for a scene of {self._pp_points} points")
+        self._check(self.L.mc_ev_add_scan_clustered(self.h, p, dev))
+
+    def ev_add_matches(self, tables):
+        """mc_ev_add_matches: a scan as its tables (dict with the keys of ``ev_scan``)."""
+        a = {k: np.ascontiguousarray(tables[k], dt) for k, dt in EV_TABLE_KEYS}
+        if not (len(a["gt_cls"]) == len(a["gt_id"]) == len(a["gt_vert"]) and
+                len(a["pr_cls"]) == len(a["pr_vert"]) == len(a["pr_void"]) == len(a["pr_score"]) and
+                len(a["pair_pred"]) == len(a["pair_gt"]) == len(a["pair_int"])):
+            raise ValueError("ev_add_matches: table columns differ in length")
+        self._check(self.L.mc_ev_add_matches(self.h, len(a["gt_cls"]), _ptr(a["gt_cls"]), _ptr(a["gt_id"]), _ptr(a["gt_vert"]),
+                                             len(a["pr_cls"]), _ptr(a["pr_cls"]), _ptr(a["pr_vert"]), _ptr(a["pr_void"]),
+                                             _ptr(a["pr_score"]), len(a["pair_pred"]), _ptr(a["pair_pred"]),
+                                             _ptr(a["pair_gt"]), _ptr(a["pair_int"])))
+
+    def ev_scan(self):
+        """mc_ev_scan_info + mc_ev_get_scan: the last added scan's tables."""
+        g, k, n = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self._check(self.L.mc_ev_scan_info(self.h, ctypes.byref(g), ctypes.byref(k), ctypes.byref(n)))
+        size = {"gt": g.value, "pr": k.value, "pa": n.value}
+        r = {key: np.zeros(max(size[key[:2]], 1), dt) for key, dt in EV_TABLE_KEYS}
+        self._check(self.L.mc_ev_get_scan(self.h, *[_ptr(r[key]) for key, _ in EV_TABLE_KEYS]))
+        return {key: r[key][:size[key[:2]]] for key, _ in EV_TABLE_KEYS}
+
+    def ev_ap(self):
+        """mc_ev_ap: (ap [C, O], stats [C, O, 4]: examples, true examples, hard false negatives, flags)."""
+        C, O = self._ev_shape
+        ap, stats = np.zeros((C, O), np.float64), np.zeros((C, O, 4), np.int64)
+        self._check(self.L.mc_ev_ap(self.h, _ptr(ap), _ptr(stats)))
+        return ap, stats
+
+    def ev_curve(self, class_index, overlap_index):
+        """mc_ev_get_curve: (scores ascending, tp, fp, fn) of a cell, empty for a cell without a curve."""
+        n = ctypes.c_int64(0)
+        self._check(self.L.mc_ev_get_curve(self.h, int(class_index), int(overlap_index), ctypes.byref(n), None, None, None, None))
+        sc = np.zeros(max(n.value, 1), np.float64)
+        tp, fp, fn = (np.zeros(max(n.value, 1), np.int64) for _ in range(3))
+        if n.value:
+            self._check(self.L.mc_ev_get_curve(self.h, int(class_index), int(overlap_index), ctypes.byref(n), _ptr(sc), _ptr(tp),
+                                               _ptr(fp), _ptr(fn)))
+        return sc[:n.value], tp[:n.value], fp[:n.value], fn[:n.value]
+
+    for f in (ev_begin, ev_add_scan, ev_add_scan_clustered, ev_add_matches, ev_scan, ev_ap, ev_curve):
+        setattr(Context, f.__name__, f)
+
+
+_ev_methods()
 
 
 def _ov_methods():

@@ -18,6 +18,7 @@
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
 #include "mc_eval_kernels.inl"
+#include "mc_ap_kernels.inl"
 #include "mc_io_kernels.inl"
 #include "mc_shard_kernels.inl"
 #include "mc_ov_kernels.inl"
@@ -104,6 +105,39 @@ struct BpState {
     DevBuf pts;  // the masks' point lists
     std::vector<int32_t> col, label, stats;
     std::vector<int64_t> off;
+};
+
+// AP evaluation state of a context (the host code is mc_ap_host.inl)
+struct EvTables {  // one scan's compact tables (include/mcgraph.h, mc_ev_get_scan)
+    std::vector<int32_t> gcls, gid, pcls, ppred, pgt;
+    std::vector<int64_t> gvert, pvert, pvoid, pint;
+    std::vector<double> pscore;
+};
+
+struct EvState {
+    bool active = false;
+    int C = 0, O = 0, nlab = 0;
+    int64_t min_region = 100;
+    bool no_class = false;
+    std::vector<int32_t> class_ids;
+    std::vector<double> overlaps;
+    DevBuf d_lab2cls, d_overlaps;
+    // accumulated over the scans: examples in per-unit regions, one unit per (scan, class, overlap)
+    int64_t ex_used = 0;
+    int units = 0;
+    DevBuf d_ex_key, d_ex_true, d_unit_cell, d_unit_off, d_unit_cnt, d_hardfn, d_flags;
+    EvTables last;
+    bool have_last = false;
+    // the table of the last mc_ev_ap
+    bool ap_valid = false;
+    std::vector<double> ap;
+    std::vector<int64_t> stats;
+    std::vector<int32_t> ndist;
+    DevBuf d_key, d_true, d_prec, d_rec, d_cell, d_ap, d_stats, d_ndist;
+    // scratch of one mc_ev_add_scan / commit
+    std::vector<int64_t> h_out;
+    DevBuf d_info, d_in[5], d_cnt, d_inst, d_tmp_id, d_class, d_gcls, d_gid, d_gvert, d_pinst, d_pk, d_pair_gt, d_pair_int,
+        d_out, d_words, d_tmp;
 };
 
 }  // namespace
@@ -196,6 +230,8 @@ struct mc_ctx {
     std::vector<int32_t> pp_fslot, pp_fin, pp_fin_node;  // object -> final slot; final objects, their nodes
     std::vector<int64_t> pp_opoff, pp_omoff;             // point / mask list offsets of the final objects
     DevBuf d_pp_fslot, d_pp_finobj, d_pp_finnode, d_pp_opoff, d_pp_omoff, d_pp_opts, d_pp_omask, d_pp_ocov, d_pp_repre;
+
+    EvState ev;  // AP evaluation (mc_ev_*)
 };
 
 namespace {
@@ -2644,3 +2680,5 @@ int mc_openvoc_query(mc_ctx *ctx, int32_t num_objects, const int64_t *obj_off, c
 }
 
 }  // extern "C"
+
+#include "mc_ap_host.inl"

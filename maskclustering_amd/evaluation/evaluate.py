@@ -7,14 +7,16 @@ mask (:308, on the GPU through torch).  Here that product, the vertex counts and
 intersections of all masks of a scan are one C-ABI call (``mc_eval_match_counts``: a per-point
 histogram over the [P, K] prediction matrix), and the match lists are rebuilt exactly as the
 reference builds them (same dict layout, order and number types).  AP (``evaluate_matches``
-:53-205) and the reports stay the reference's.
+:53-205) runs on the device as well: the match dicts are packed into tables
+(``pack_matches``), added scan by scan (``mc_ev_add_matches``) and ``mc_ev_ap`` gives the
+[1, classes, overlaps] array.  ``compute_averages`` and the reports stay the reference's.
 
 Run from the reference's root instead of ``python -m evaluation.evaluate ...``:
 
     python -m maskclustering_amd.evaluation.evaluate --pred_path ... --gt_path ... --dataset scannet [--no_class]
 
 which imports the reference's module (its argument parsing and tables), routes its
-``assign_instances_for_scan`` here and runs its ``main``.
+``assign_instances_for_scan`` and ``evaluate_matches`` here and runs its ``main``.
 """
 from __future__ import annotations
 
@@ -103,10 +105,51 @@ def assign_instances_for_scan(pred_file, gt_file, ev=None):
     return gt2pred, pred2gt
 
 
+def pack_matches(gt2pred, pred2gt, class_labels):
+    """One scan's two match dicts as the tables of ``Context.ev_add_matches``: ground truths by class
+    in the table's order, predictions by ``pred_id``, and the pairs in each ground truth's
+    ``matched_pred`` order (the order the greedy pass walks them in)."""
+    gt_cls, gt_id, gt_vert, pairs = [], [], [], []
+    preds = {}
+    for c, label in enumerate(class_labels):
+        for p in pred2gt.get(label, ()):
+            preds[p['filename']] = (c, p)
+    order = sorted(preds, key=lambda f: preds[f][1]['pred_id'])
+    index = {f: i for i, f in enumerate(order)}
+    for c, label in enumerate(class_labels):
+        for gt in gt2pred.get(label, ()):
+            g = len(gt_cls)
+            gt_cls.append(c)
+            gt_id.append(int(gt['instance_id']))
+            gt_vert.append(int(gt['vert_count']))
+            for p in gt['matched_pred']:
+                pairs.append((index[p['filename']], g, int(p['intersection'])))
+    pr = [preds[f] for f in order]
+    return dict(gt_cls=np.array(gt_cls, np.int32), gt_id=np.array(gt_id, np.int32), gt_vert=np.array(gt_vert, np.int64),
+                pr_cls=np.array([c for c, _ in pr], np.int32), pr_vert=np.array([int(p['vert_count']) for _, p in pr], np.int64),
+                pr_void=np.array([int(p['void_intersection']) for _, p in pr], np.int64),
+                pr_score=np.array([float(p['confidence']) for _, p in pr], np.float64),
+                pair_pred=np.array([t[0] for t in pairs], np.int32), pair_gt=np.array([t[1] for t in pairs], np.int32),
+                pair_int=np.array([t[2] for t in pairs], np.int64))
+
+
+def evaluate_matches(matches, ev=None):
+    """evaluation/evaluate.py:53-205 on the device: the [1, classes, overlaps] AP array of the
+    reference (equal up to the summation order of its final dot product)."""
+    if ev is None:
+        ev = sys.modules["evaluation.evaluate"]
+    ctx = _device.context()
+    ctx.ev_begin(ev.VALID_CLASS_IDS, ev.opt.overlaps, int(ev.opt.min_region_sizes[0]), bool(ev.opt.no_class))
+    for m in matches:
+        ctx.ev_add_matches(pack_matches(matches[m]['gt'], matches[m]['pred'], ev.CLASS_LABELS))
+    return ctx.ev_ap()[0][None]
+
+
 def main():
     import importlib
     ev = importlib.import_module("evaluation.evaluate")        # the reference's: parses sys.argv
     ev.assign_instances_for_scan = lambda pred_file, gt_file: assign_instances_for_scan(pred_file, gt_file, ev)
+    ev.evaluate_matches = lambda matches: evaluate_matches(matches, ev)
     ev.main()
 
 

@@ -250,3 +250,15 @@ def make_frames_shape(name: str, seed: int = 0, device: str = "cpu", **kw) -> Sc
     params = dict(FRAME_SHAPES[name])
     params.update(kw)
     return make_frames(seed=seed, device=device, **params)
+
+
+def slab_ground_truth(points, class_ids, width=0.25):
+    """Deterministic ground-truth ids for a synthetic scene (the AP evaluation's tests and A/B script):
+    instance = ``width``-metre slab along x (counted from the scene's lowest slab), class =
+    ``class_ids[slab % 3]``, id = class * 1000 + slab + 1, every seventh slab left 0 (unlabelled)."""
+    x = np.asarray(points, np.float64)[:, 0]
+    slab = np.floor(x / width).astype(np.int64)
+    slab -= slab.min() if len(slab) else 0
+    ids = np.asarray(class_ids, np.int64)[slab % 3] * 1000 + slab + 1
+    ids[slab % 7 == 6] = 0
+    return ids.astype(np.int32)
