@@ -277,7 +277,11 @@ int mc_ctx_attach_comm(mc_ctx *ctx, void *nccl_comm);
 /* ---- post-processing of the clustered objects ----------------------
  * Replaces the compute of utils/post_process.py:173-194 (post_process up to export):
  * dbscan_process (:104-123), filter_point (:40-101), merge_overlapping_objects (:7-37).
- * Inputs are host arrays.  Nodes are the ones post_process keeps (>= 2 masks, :182), their
+ * Inputs are host arrays; checks as mc_pp_run_device (the arrays are uploaded and checked by the
+ * same kernels: an offset array that is not ascending or exceeds its table, mask_off included, an
+ * index out of range and a frame that is not visible are MC_ERR_INVALID, a node spanning more
+ * than 2^21 DBSCAN cells is MC_ERR_UNSUPPORTED; of several defects the first in this order is
+ * reported).  Nodes are the ones post_process keeps (>= 2 masks, :182), their
  * points in list(node.point_ids) order (graph/node.py:45); node masks are indices into the
  * mask table (mask_point_clouds entries) in node.mask_list order, with the frame column of
  * each.  A node mask whose frame is not among the node's visible frames fails with

@@ -14,6 +14,7 @@
 
 #include "mc_internal.hpp"
 #include "mc_bp_plan.hpp"
+#include "mc_pp_plan.hpp"
 #include "mc_kernels.inl"
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
@@ -1754,739 +1755,9 @@ int mc_cluster_get_objects(mc_ctx *ctx, uint64_t *vf_bits, int64_t *c_off, int32
 
 #include "mc_bp_host.inl"
 
-// ---------------------------------------------------------------------------------------------
-// post-processing (utils/post_process.py:173-194)
-// ---------------------------------------------------------------------------------------------
-
-namespace {
-
-// a device array of the post-processing core (a buffer of the call, or the caller's pointer)
-struct PPPtr {
-    const void *ptr = nullptr;
-    template <typename T> T *as() const { return static_cast<T *>(const_cast<void *>(ptr)); }
-};
-
-// Sizes and arrays of one post-processing run, all on the device.  The node arrays (point and mask
-// offsets, points, masks) are the context's own d_pp_* buffers, which the export reads later.
-struct PPIn {
-    int64_t P = 0, E = 0, Q = 0, H = 0;
-    int F = 0, Mt = 0, N = 0;
-    PPPtr scene, pfm, moff, mpts, nvf, qfp, hoff, dorder;
-    const int64_t *h_npoff = nullptr;  // host: node point offsets (node sizes for the big-node items)
-    const int32_t *h_order = nullptr;  // host: the size order
-};
-
-// entry_object / mask_object / mask_coverage on the host (mc_pp_get_results)
-void pp_fetch_host(mc_ctx *ctx)
-{
-    if (ctx->pp_host) return;
-    hipStream_t s = ctx->stream;
-    const int64_t E = ctx->pp_info.num_entries, Q = ctx->pp_info.num_node_masks;
-    ctx->pp_entry_obj.resize(E);
-    ctx->pp_qobj.resize(Q);
-    ctx->pp_qcov.resize(Q);
-    if (E) MC_HIP(hipMemcpyAsync(ctx->pp_entry_obj.data(), ctx->d_pp_eobj.ptr, E * 4, hipMemcpyDeviceToHost, s));
-    if (Q) {
-        MC_HIP(hipMemcpyAsync(ctx->pp_qobj.data(), ctx->d_pp_qobj.ptr, Q * 4, hipMemcpyDeviceToHost, s));
-        MC_HIP(hipMemcpyAsync(ctx->pp_qcov.data(), ctx->d_pp_qcov.ptr, Q * 8, hipMemcpyDeviceToHost, s));
-    }
-    MC_HIP(hipStreamSynchronize(s));
-    ctx->timer.collect();
-    for (auto &o : ctx->pp_entry_obj)
-        if (o >= 0 && ctx->pp_state[o] != 2) o = -1;
-    ctx->pp_host = true;
-}
-
-// dbscan_process, filter_point and merge_overlapping_objects of the nodes in `in`; host_results also
-// brings the per-entry results to the host (mc_pp_run), else they stay on the device until asked for
-void pp_core(mc_ctx *ctx, const mc_pp_params *params, const PPIn &in, bool host_results)
-{
-    {
-        const int N = in.N, F = in.F, FW = (F + 63) / 64;
-        const int64_t P = in.P, E = in.E, Q = in.Q;
-        const int64_t *node_pt_off = in.h_npoff;
-        const int32_t *order = in.h_order;
-        const PPPtr scene = in.scene, pfm = in.pfm, moff = in.moff, mpts = in.mpts, nvf = in.nvf, qfp = in.qfp,
-                    hoff = in.hoff, dorder = in.dorder;
-        const PPPtr npoff{ctx->d_pp_npoff.ptr}, npts{ctx->d_pp_npts.ptr}, qoff{ctx->d_pp_qoff.ptr}, qm{ctx->d_pp_qm.ptr};
-        hipStream_t s = ctx->stream;
-        auto up = [&](DevBuf &b, const void *h, size_t bytes) {
-            b.reserve(bytes + 8);
-            if (bytes) MC_HIP(hipMemcpyAsync(b.ptr, h, bytes, hipMemcpyHostToDevice, s));
-        };
-        mc::PPDev pr;
-        pr.eps2 = params->dbscan_eps * params->dbscan_eps;
-        pr.ce = params->dbscan_eps * 1.01;
-        pr.thr = params->point_filter_threshold;
-        pr.ratio = params->overlapping_ratio;
-        pr.minpts = params->dbscan_min_points;
-
-        // ---- DBSCAN split (dbscan_process) ----
-        DevBuf xyz, pcell, pbkt, bcnt, bstart, blist, ncnt, par, root, rnk, lab, ccnt, nob, nsh, tick, skey, sxyz, sidx;
-        skey.reserve(E * 8 + 8);  // bucket-ordered copies of the cell keys, points and indices
-        sxyz.reserve(E * 24 + 8);
-        sidx.reserve(E * 4 + 8);
-        xyz.reserve(E * 24 + 8);
-        pcell.reserve(E * 8 + 8);
-        for (DevBuf *b : {&pbkt, &blist, &ncnt, &par, &root, &rnk, &lab}) b->reserve(E * 4 + 8);
-        bcnt.reserve((2 * E + N + 1) * 4);
-        bstart.reserve((2 * E + N + 1) * 4);
-        ccnt.reserve((E + N + 1) * 4);
-        nob.reserve(N * 4 + 8);
-        nsh.reserve(N * 4 + 8);
-        tick.reserve(16);
-        MC_HIP(hipMemsetAsync(bcnt.ptr, 0, (2 * E + N + 1) * 4, s));
-        MC_HIP(hipMemsetAsync(tick.ptr, 0, 16, s));
-        {
-            mc::TimedScope ts(ctx->timer, s, "pp_dbscan");
-            if (E) hipLaunchKernelGGL(mc::k_pp_gather, grid_for(3 * E), dim3(256), 0, s, scene.as<double>(), npts.as<int>(), E,
-                                      xyz.as<double>());
-            // nodes above big_min points (the first nbig of the size order) are split over the chip
-            int big_min = mc::kPPLdsUF;
-            if (const char *e = getenv("MC_PP_BIG_MIN")) big_min = std::max(1, atoi(e));
-            int nbig = 0;
-            std::vector<int2> items;
-            while (nbig < N && node_pt_off[order[nbig] + 1] - node_pt_off[order[nbig]] > big_min) {
-                const int k = order[nbig++];
-                const int n = static_cast<int>(node_pt_off[k + 1] - node_pt_off[k]);
-                for (int c = 0; c < n; c += 512) items.push_back(make_int2(k, c));
-            }
-            if (nbig) {
-                DevBuf ditems, gcm;
-                up(ditems, items.data(), items.size() * sizeof(int2));
-                gcm.reserve(static_cast<size_t>(N) * 12 + 8);
-                const mc::PPBig b{npoff.as<int64_t>(), xyz.as<double>(), pcell.as<unsigned long long>(), pbkt.as<int>(),
-                                  bcnt.as<int>(), bstart.as<int>(), blist.as<int>(), ncnt.as<int>(), par.as<int>(),
-                                  root.as<int>(), rnk.as<int>(), lab.as<int>(), ccnt.as<int>(), gcm.as<int>()};
-                const int ni = static_cast<int>(items.size());
-                hipLaunchKernelGGL(mc::k_pp_big_grid<512>, dim3(nbig), dim3(512), 0, s, nbig, dorder.as<int>(), pr, b);
-                hipLaunchKernelGGL((mc::k_pp_big_walk<512, 0>), dim3(std::min(ni, 65536)), dim3(512), 0, s, ni,
-                                   ditems.as<int2>(), pr, b);
-                hipLaunchKernelGGL((mc::k_pp_big_walk<512, 1>), dim3(std::min(ni, 65536)), dim3(512), 0, s, ni,
-                                   ditems.as<int2>(), pr, b);
-                hipLaunchKernelGGL(mc::k_pp_big_label<512>, dim3(nbig), dim3(512), 0, s, nbig, dorder.as<int>(), pr, b,
-                                   nob.as<int>(), nsh.as<int>());
-                MC_HIP(hipGetLastError());
-                MC_HIP(hipStreamSynchronize(s));  // ditems / gcm are freed at scope exit
-            }
-            if (N > nbig)  // 512-thread workgroups (1024 spills the neighbour walks)
-                hipLaunchKernelGGL(mc::k_pp_dbscan<512>, dim3(std::max(1, std::min(N - nbig, ctx->num_cu * 2))), dim3(512), 0, s,
-                                   N - nbig, dorder.as<int>() + nbig, tick.as<int>(),
-                                      npoff.as<int64_t>(), pr, xyz.as<double>(), pcell.as<unsigned long long>(), pbkt.as<int>(),
-                                      bcnt.as<int>(), bstart.as<int>(), blist.as<int>(), ncnt.as<int>(), par.as<int>(),
-                                      root.as<int>(), rnk.as<int>(), lab.as<int>(), ccnt.as<int>(), nob.as<int>(), nsh.as<int>(),
-                                      skey.as<unsigned long long>(), sxyz.as<double>(), sidx.as<int>());
-            MC_HIP(hipGetLastError());
-        }
-        std::vector<int32_t> h_nob(N), h_base(N + 1, 0);
-        if (N) MC_HIP(hipMemcpyAsync(h_nob.data(), nob.ptr, N * 4, hipMemcpyDeviceToHost, s));
-        MC_HIP(hipStreamSynchronize(s));
-        for (int k = 0; k < N; k++) h_base[k + 1] = h_base[k] + h_nob[k];
-        const int K = h_base[N];
-        DevBuf obase;
-        up(obase, h_base.data(), static_cast<size_t>(N + 1) * 4);
-
-        // ---- filter_point ----
-        const int slots = std::max(1, std::min(N, ctx->num_cu));
-        if (ctx->pp_posmap_P < P || ctx->pp_posmap_slots < slots) {
-            ctx->d_pp_posmap.release();
-            ctx->d_pp_posmap.reserve(static_cast<size_t>(slots) * P * 4 + 8);
-            MC_HIP(hipMemsetAsync(ctx->d_pp_posmap.ptr, 0xFF, static_cast<size_t>(slots) * P * 4, s));
-            ctx->pp_posmap_P = P;
-            ctx->pp_posmap_slots = slots;
-        }
-        const int64_t H = in.H;
-        DevBuf hit, cvid, qobj, qcov, onm, onv, obox, eobj;
-        hit.reserve(H * 8 + 8);
-        cvid.reserve(E * 4 + 8);
-        qobj.reserve(Q * 4 + 8);
-        qcov.reserve(Q * 8 + 8);
-        onm.reserve(K * 4 + 8);
-        onv.reserve(K * 4 + 8);
-        obox.reserve(K * 48 + 8);
-        eobj.reserve(E * 4 + 8);
-        if (H) MC_HIP(hipMemsetAsync(hit.ptr, 0, H * 8, s));
-        if (K) MC_HIP(hipMemsetAsync(onm.ptr, 0, K * 4, s));
-        {
-            mc::TimedScope ts(ctx->timer, s, "pp_filter");
-            if (N) hipLaunchKernelGGL(mc::k_pp_filter, dim3(slots), dim3(256), 0, s, N, dorder.as<int>(), tick.as<int>() + 1, pr,
-                                      FW, P, npoff.as<int64_t>(), npts.as<int>(), nvf.as<unsigned long long>(),
-                                      hoff.as<int64_t>(), qoff.as<int64_t>(), qm.as<int>(), qfp.as<int>(), moff.as<int64_t>(),
-                                      mpts.as<int>(), pfm.as<unsigned long long>(), xyz.as<double>(), lab.as<int>(),
-                                      ccnt.as<int>(), nob.as<int>(), nsh.as<int>(), obase.as<int>(), ctx->d_pp_posmap.as<int>(),
-                                      hit.as<unsigned long long>(), cvid.as<int>(), qobj.as<int>(), qcov.as<double>(),
-                                      onm.as<int>(), onv.as<int>(), obox.as<double>(), eobj.as<int>());
-            MC_HIP(hipGetLastError());
-        }
-        std::vector<int32_t> h_nm(K), h_nv(K);
-        std::vector<double> h_box(static_cast<size_t>(K) * 6);
-        if (K) {
-            MC_HIP(hipMemcpyAsync(h_nm.data(), onm.ptr, K * 4, hipMemcpyDeviceToHost, s));
-            MC_HIP(hipMemcpyAsync(h_nv.data(), onv.ptr, K * 4, hipMemcpyDeviceToHost, s));
-            MC_HIP(hipMemcpyAsync(h_box.data(), obox.ptr, K * 48, hipMemcpyDeviceToHost, s));
-        }
-        MC_HIP(hipStreamSynchronize(s));
-        // objects kept by filter_point (:96): a kept point and >= 2 masks
-        std::vector<int32_t> kidx(K, -1), kept;
-        std::vector<double> kbox;
-        std::vector<int32_t> klen;
-        for (int o = 0; o < K; o++)
-            if (h_nv[o] > 0 && h_nm[o] >= 2) {
-                kidx[o] = static_cast<int32_t>(kept.size());
-                kept.push_back(o);
-                kbox.insert(kbox.end(), h_box.begin() + 6 * o, h_box.begin() + 6 * o + 6);
-                klen.push_back(h_nv[o]);
-            }
-        const int Kk = static_cast<int>(kept.size());
-        MC_REQUIRE(Kk <= 46340, MC_ERR_UNSUPPORTED, "more than 46340 objects after filter_point");
-
-        // ---- merge_overlapping_objects ----
-        std::vector<uint8_t> h_inv(Kk, 0);
-        if (Kk > 1) {
-            mc::TimedScope ts(ctx->timer, s, "pp_merge");
-            DevBuf dk, pcnt, plist, mxc, inter, dbox, dlen, dec, inv;
-            up(dk, kidx.data(), static_cast<size_t>(K) * 4);
-            up(dbox, kbox.data(), static_cast<size_t>(Kk) * 48);
-            up(dlen, klen.data(), static_cast<size_t>(Kk) * 4);
-            pcnt.reserve(P * 4 + 8);
-            mxc.reserve(8);
-            int sl = mc::kPPSlots;
-            for (int pass = 0; pass < 2; pass++) {
-                plist.reserve(static_cast<size_t>(P) * sl * 4 + 8);
-                MC_HIP(hipMemsetAsync(pcnt.ptr, 0, P * 4, s));
-                MC_HIP(hipMemsetAsync(mxc.ptr, 0, 4, s));
-                hipLaunchKernelGGL(mc::k_pp_index, grid_for(E), dim3(256), 0, s, E, npts.as<int>(), eobj.as<int>(), dk.as<int>(),
-                                   sl, pcnt.as<int>(), plist.as<int>(), mxc.as<int>());
-                int mx = 0;
-                MC_HIP(hipMemcpyAsync(&mx, mxc.ptr, 4, hipMemcpyDeviceToHost, s));
-                MC_HIP(hipStreamSynchronize(s));
-                if (mx <= sl) break;
-                sl = mx;
-            }
-            inter.reserve(static_cast<size_t>(Kk) * Kk * 4);
-            dec.reserve(static_cast<size_t>(Kk) * Kk);
-            inv.reserve(Kk + 8);
-            MC_HIP(hipMemsetAsync(inter.ptr, 0, static_cast<size_t>(Kk) * Kk * 4, s));
-            hipLaunchKernelGGL(mc::k_pp_pairs, grid_for(P), dim3(256), 0, s, P, sl, pcnt.as<int>(), plist.as<int>(), Kk,
-                               inter.as<int>());
-            int kCap = 1 << 16;  // non-zero decisions handled by the host pass; more: k_pp_greedy
-            if (const char *e = getenv("MC_PP_GREEDY_CAP")) kCap = std::max(0, atoi(e));  // tests force the device pass
-            DevBuf nl, lst;
-            nl.reserve(8);
-            lst.reserve(static_cast<size_t>(std::max(kCap, 1)) * sizeof(int2));
-            MC_HIP(hipMemsetAsync(nl.ptr, 0, 4, s));
-            hipLaunchKernelGGL(mc::k_pp_decide, grid_for(static_cast<int64_t>(Kk) * Kk), dim3(256), 0, s, Kk, pr,
-                               dbox.as<double>(), dlen.as<int>(), inter.as<int>(), dec.as<unsigned char>(), kCap,
-                               nl.as<int>(), lst.as<int2>());
-            MC_HIP(hipGetLastError());
-            int nd = 0;
-            MC_HIP(hipMemcpyAsync(&nd, nl.ptr, 4, hipMemcpyDeviceToHost, s));
-            MC_HIP(hipStreamSynchronize(s));
-            if (nd <= kCap) {
-                // the greedy pass (post_process.py:14-29) over the non-zero decisions only: zero
-                // decisions change nothing, so visiting (i, j) ascending is the reference's loop
-                std::vector<int2> d(nd);
-                if (nd) MC_HIP(hipMemcpy(d.data(), lst.ptr, static_cast<size_t>(nd) * sizeof(int2), hipMemcpyDeviceToHost));
-                auto jj = [](const int2 &v) { return v.y < 0 ? -1 - v.y : v.y; };
-                std::sort(d.begin(), d.end(), [&](const int2 &a, const int2 &b) {
-                    return a.x != b.x ? a.x < b.x : jj(a) < jj(b);
-                });
-                int row = -1;
-                bool skip = false;
-                for (const int2 &v : d) {
-                    if (v.x != row) {  // "if invalid_object[i]: continue" is read once per row (:15)
-                        row = v.x;
-                        skip = h_inv[row] != 0;
-                    }
-                    if (skip || h_inv[jj(v)]) continue;
-                    if (v.y < 0) h_inv[v.x] = 1;
-                    else h_inv[v.y] = 1;
-                }
-            } else {
-                hipLaunchKernelGGL(mc::k_pp_greedy, dim3(1), dim3(1024), 0, s, Kk, dec.as<unsigned char>(), inv.as<unsigned char>());
-                MC_HIP(hipGetLastError());
-                MC_HIP(hipMemcpyAsync(h_inv.data(), inv.ptr, Kk, hipMemcpyDeviceToHost, s));
-                MC_HIP(hipStreamSynchronize(s));  // h_inv is pageable host memory read just below
-            }
-        }
-        // ---- results ----
-        ctx->pp_state.assign(K, 0);
-        int nfin = 0;
-        for (int i = 0; i < Kk; i++) {
-            ctx->pp_state[kept[i]] = h_inv[i] ? 1 : 2;
-            nfin += h_inv[i] ? 0 : 1;
-        }
-        ctx->pp_obj_node.resize(K);
-        for (int k = 0; k < N; k++)
-            for (int o = h_base[k]; o < h_base[k + 1]; o++) ctx->pp_obj_node[o] = k;
-        ctx->pp_box = std::move(h_box);
-        ctx->pp_info.num_objects = K;
-        ctx->pp_info.num_filtered = Kk;
-        ctx->pp_info.num_final = nfin;
-        ctx->pp_info.num_entries = E;
-        ctx->pp_info.num_node_masks = Q;
-        // the final objects in DBSCAN-object order (the reference's total_*_list order after the
-        // merge), the sizes of their point and mask lists (counted by k_pp_filter)
-        ctx->pp_fslot.assign(K, -1);
-        ctx->pp_fin.clear();
-        ctx->pp_fin_node.clear();
-        ctx->pp_opoff.assign(1, 0);
-        ctx->pp_omoff.assign(1, 0);
-        for (int o = 0; o < K; o++)
-            if (ctx->pp_state[o] == 2) {
-                ctx->pp_fslot[o] = static_cast<int32_t>(ctx->pp_fin.size());
-                ctx->pp_fin.push_back(o);
-                ctx->pp_fin_node.push_back(ctx->pp_obj_node[o]);
-                ctx->pp_opoff.push_back(ctx->pp_opoff.back() + h_nv[o]);
-                ctx->pp_omoff.push_back(ctx->pp_omoff.back() + h_nm[o]);
-            }
-        // the per-entry results stay on the device for the export
-        ctx->d_pp_eobj.swap(eobj);
-        ctx->d_pp_qobj.swap(qobj);
-        ctx->d_pp_qcov.swap(qcov);
-        ctx->pp_P = P;
-        ctx->pp_host = ctx->pp_export = false;
-        if (host_results) pp_fetch_host(ctx);
-        else {
-            MC_HIP(hipStreamSynchronize(s));
-            ctx->timer.collect();
-        }
-        ctx->have_pp = true;
-    }
-}
-
-}  // namespace
+#include "mc_pp_host.inl"
 
 extern "C" {
-
-int mc_pp_run(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points, int32_t num_frames, const double *scene_xyz,
-              const uint64_t *pfm_bits, int32_t num_masks, const int64_t *mask_off, const int32_t *mask_pts,
-              int32_t num_nodes, const uint64_t *node_vf_bits, const int64_t *node_pt_off, const int32_t *node_pts,
-              const int64_t *node_mask_off, const int32_t *node_masks, const int32_t *node_mask_col)
-{
-    return guarded(ctx, [&] {
-        ctx->have_pp = false;
-        MC_REQUIRE(params, MC_ERR_INVALID, "null params");
-        MC_REQUIRE(num_points >= 0 && num_points < (1ll << 31) && num_frames >= 0 && num_masks >= 0 && num_nodes >= 0,
-                   MC_ERR_INVALID, "bad sizes");
-        MC_REQUIRE(num_frames <= 16384, MC_ERR_UNSUPPORTED, "num_frames must be <= 16384");
-        MC_REQUIRE(params->dbscan_eps > 0 && params->dbscan_min_points >= 1, MC_ERR_INVALID, "bad DBSCAN parameters");
-        MC_REQUIRE(mask_off && node_pt_off && node_mask_off, MC_ERR_INVALID, "null offsets");
-        const int N = num_nodes, F = num_frames, FW = (F + 63) / 64, Mt = num_masks;
-        const int64_t P = num_points, E = node_pt_off[N], Q = node_mask_off[N], MP = mask_off[Mt];
-        MC_REQUIRE(node_pt_off[0] == 0 && node_mask_off[0] == 0 && mask_off[0] == 0, MC_ERR_INVALID, "offsets must start at 0");
-        MC_REQUIRE(E < (1ll << 30) && Q < (1ll << 31), MC_ERR_UNSUPPORTED, "too many node points");
-        MC_REQUIRE((P == 0 || (scene_xyz && pfm_bits)) && (E == 0 || node_pts) && (Q == 0 || (node_masks && node_mask_col)) &&
-                       (MP == 0 || mask_pts) && (N == 0 || node_vf_bits),
-                   MC_ERR_INVALID, "null argument");
-        // host checks and per-node layout: the frame position of each node mask among the node's
-        // visible frames (post_process.py:69), hit-bit words per node point
-        std::vector<int32_t> qfpos(static_cast<size_t>(Q));
-        std::vector<int64_t> hit_off(N + 1, 0);
-        std::vector<int32_t> order(N);
-        for (int k = 0; k < N; k++) {
-            const uint64_t *vf = node_vf_bits + static_cast<int64_t>(k) * FW;
-            int nvf = 0;
-            for (int w = 0; w < FW; w++) nvf += __builtin_popcountll(vf[w]);
-            const int64_t n = node_pt_off[k + 1] - node_pt_off[k];
-            MC_REQUIRE(n >= 0 && node_mask_off[k + 1] >= node_mask_off[k], MC_ERR_INVALID, "offsets must be ascending");
-            for (int64_t q = node_mask_off[k]; q < node_mask_off[k + 1]; q++) {
-                const int c = node_mask_col[q], m = node_masks[q];
-                MC_REQUIRE(m >= 0 && m < Mt, MC_ERR_INVALID, "node mask index out of range");
-                MC_REQUIRE(c >= 0 && c < F && ((vf[c >> 6] >> (c & 63)) & 1ull), MC_ERR_INVALID,
-                           "a mask's frame is not among the node's visible frames (post_process.py:69 IndexError)");
-                int pos = 0;
-                for (int w = 0; w < (c >> 6); w++) pos += __builtin_popcountll(vf[w]);
-                pos += __builtin_popcountll(vf[c >> 6] & ((1ull << (c & 63)) - 1));
-                qfpos[q] = pos;
-            }
-            hit_off[k + 1] = hit_off[k] + n * ((nvf + 63) / 64);
-            order[k] = k;
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            return node_pt_off[a + 1] - node_pt_off[a] > node_pt_off[b + 1] - node_pt_off[b];
-        });
-        for (int64_t i = 0; i < E; i++) MC_REQUIRE(node_pts[i] >= 0 && node_pts[i] < P, MC_ERR_INVALID, "node point out of range");
-        {  // the DBSCAN grid packs cell coordinates in 21 bits per axis (pack3): every node's extent
-           // must stay below 2^21 cells of 1.01 eps, or neighbours would be missed silently
-            const double ce = params->dbscan_eps * 1.01;
-            for (int k = 0; k < N; k++) {
-                double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-                for (int64_t i = node_pt_off[k]; i < node_pt_off[k + 1]; i++)
-                    for (int c = 0; c < 3; c++) {
-                        const double v = scene_xyz[3 * static_cast<int64_t>(node_pts[i]) + c];
-                        mn[c] = std::min(mn[c], v);
-                        mx[c] = std::max(mx[c], v);
-                    }
-                for (int c = 0; c < 3; c++)
-                    MC_REQUIRE(!(mx[c] >= mn[c]) || std::floor((mx[c] - mn[c]) / ce) < double((1 << 21) - 1),
-                               MC_ERR_UNSUPPORTED, "a node spans more than 2^21 DBSCAN cells per axis (eps too small)");
-            }
-        }
-        for (int64_t i = 0; i < MP; i++) MC_REQUIRE(mask_pts[i] >= 0 && mask_pts[i] < P, MC_ERR_INVALID, "mask point out of range");
-
-        hipStream_t s = ctx->stream;
-        auto up = [&](DevBuf &b, const void *h, size_t bytes) {
-            b.reserve(bytes + 8);
-            if (bytes) MC_HIP(hipMemcpyAsync(b.ptr, h, bytes, hipMemcpyHostToDevice, s));
-        };
-        DevBuf scene, pfm, moff, mpts, nvf, qfp, hoff, dorder;
-        up(scene, scene_xyz, static_cast<size_t>(P) * 24);
-        up(pfm, pfm_bits, static_cast<size_t>(P) * FW * 8);
-        up(moff, mask_off, static_cast<size_t>(Mt + 1) * 8);
-        up(mpts, mask_pts, static_cast<size_t>(MP) * 4);
-        up(ctx->d_pp_npoff, node_pt_off, static_cast<size_t>(N + 1) * 8);
-        up(ctx->d_pp_npts, node_pts, static_cast<size_t>(E) * 4);
-        up(nvf, node_vf_bits, static_cast<size_t>(N) * FW * 8);
-        up(ctx->d_pp_qoff, node_mask_off, static_cast<size_t>(N + 1) * 8);
-        up(ctx->d_pp_qm, node_masks, static_cast<size_t>(Q) * 4);
-        up(qfp, qfpos.data(), static_cast<size_t>(Q) * 4);
-        up(hoff, hit_off.data(), static_cast<size_t>(N + 1) * 8);
-        up(dorder, order.data(), static_cast<size_t>(N) * 4);
-
-        PPIn in;
-        in.P = P, in.E = E, in.Q = Q, in.H = hit_off[N];
-        in.F = F, in.Mt = Mt, in.N = N;
-        in.scene.ptr = scene.ptr, in.pfm.ptr = pfm.ptr, in.moff.ptr = moff.ptr, in.mpts.ptr = mpts.ptr;
-        in.nvf.ptr = nvf.ptr, in.qfp.ptr = qfp.ptr, in.hoff.ptr = hoff.ptr, in.dorder.ptr = dorder.ptr;
-        in.h_npoff = node_pt_off;
-        in.h_order = order.data();
-        pp_core(ctx, params, in, true);
-    });
-}
-
-// mc_pp_run with every array on the device: the host checks and the per-node layout become kernels
-// behind one flag; the host reads the flag, the node offsets and the size order (O(num_nodes))
-static void pp_run_device(mc_ctx *ctx, const mc_pp_params *params, mc::PPArgs a)
-{
-    hipStream_t s = ctx->stream;
-    const int N = a.N;
-    MC_REQUIRE(params, MC_ERR_INVALID, "null params");
-    MC_REQUIRE(a.P >= 0 && a.P < (1ll << 31) && a.F >= 0 && a.Mt >= 0 && N >= 0, MC_ERR_INVALID, "bad sizes");
-    MC_REQUIRE(a.F <= 16384, MC_ERR_UNSUPPORTED, "num_frames must be <= 16384");
-    MC_REQUIRE(params->dbscan_eps > 0 && params->dbscan_min_points >= 1, MC_ERR_INVALID, "bad DBSCAN parameters");
-    MC_REQUIRE(a.mask_off && a.npoff && a.qoff, MC_ERR_INVALID, "null offsets");
-    a.FW = (a.F + 63) / 64;
-    int64_t ends[6];  // first and last entry of the three offset arrays
-    const int64_t *offs[3] = {a.npoff, a.qoff, a.mask_off};
-    const int lens[3] = {N, N, a.Mt};
-    for (int i = 0; i < 3; i++) {
-        MC_HIP(hipMemcpyAsync(&ends[2 * i], offs[i], 8, hipMemcpyDeviceToHost, s));
-        MC_HIP(hipMemcpyAsync(&ends[2 * i + 1], offs[i] + lens[i], 8, hipMemcpyDeviceToHost, s));
-    }
-    MC_HIP(hipStreamSynchronize(s));
-    MC_REQUIRE(ends[0] == 0 && ends[2] == 0 && ends[4] == 0, MC_ERR_INVALID, "offsets must start at 0");
-    a.E = ends[1], a.Q = ends[3], a.MP = ends[5];
-    MC_REQUIRE(a.E >= 0 && a.Q >= 0 && a.MP >= 0, MC_ERR_INVALID, "offsets must be ascending");
-    MC_REQUIRE(a.E < (1ll << 30) && a.Q < (1ll << 31), MC_ERR_UNSUPPORTED, "too many node points");
-    MC_REQUIRE((a.P == 0 || (a.scene && a.pfm)) && (a.E == 0 || a.npts) && (a.Q == 0 || (a.qm && a.qcol)) &&
-                   (a.MP == 0 || a.mask_pts) && (N == 0 || a.nvf),
-               MC_ERR_INVALID, "null argument");
-    // the node arrays stay with the context for the export
-    auto keep = [&](DevBuf &b, const void *src, size_t bytes) {
-        if (src == b.ptr) return;  // mc_pp_run_clustered built them in place
-        b.reserve(bytes + 8);
-        if (bytes) MC_HIP(hipMemcpyAsync(b.ptr, src, bytes, hipMemcpyDeviceToDevice, s));
-    };
-    keep(ctx->d_pp_npoff, a.npoff, static_cast<size_t>(N + 1) * 8);
-    keep(ctx->d_pp_npts, a.npts, static_cast<size_t>(a.E) * 4);
-    keep(ctx->d_pp_qoff, a.qoff, static_cast<size_t>(N + 1) * 8);
-    keep(ctx->d_pp_qm, a.qm, static_cast<size_t>(a.Q) * 4);
-    a.npoff = ctx->d_pp_npoff.as<int64_t>(), a.npts = ctx->d_pp_npts.as<int>();
-    a.qoff = ctx->d_pp_qoff.as<int64_t>(), a.qm = ctx->d_pp_qm.as<int>();
-
-    DevBuf qfp, hitw, hoff, nsize, dorder, flag;
-    qfp.reserve(a.Q * 4 + 8);
-    hitw.reserve(static_cast<size_t>(N) * 8 + 8);
-    hoff.reserve(static_cast<size_t>(N + 1) * 8);
-    nsize.reserve(static_cast<size_t>(N) * 4 + 8);
-    dorder.reserve(static_cast<size_t>(N) * 4 + 8);
-    flag.reserve(8);
-    MC_HIP(hipMemsetAsync(flag.ptr, 0, 4, s));
-    mc::PPDev pr{};
-    pr.ce = params->dbscan_eps * 1.01;
-    {
-        mc::TimedScope ts(ctx->timer, s, "pp_prep");
-        hipLaunchKernelGGL(mc::k_pp_validate, grid_for(std::max<int64_t>(std::max(a.E, a.MP), std::max<int64_t>(a.Q, std::max(N, a.Mt)))),
-                           dim3(256), 0, s, a, flag.as<int>());
-        if (N) {
-            hipLaunchKernelGGL(mc::k_pp_prep, dim3(std::min(N, 4096)), dim3(256), 0, s, a, pr, flag.as<int>(), qfp.as<int>(),
-                               hitw.as<int64_t>(), nsize.as<int>());
-            hipLaunchKernelGGL(mc::k_pp_order, grid_for(N), dim3(256), 0, s, N, nsize.as<int>(), flag.as<int>(),
-                               dorder.as<int>());
-        }
-        hipLaunchKernelGGL(mc::k_pp_scan64<int64_t>, dim3(1), dim3(1024), 0, s, hitw.as<int64_t>(), N, hoff.as<int64_t>());
-        MC_HIP(hipGetLastError());
-    }
-    int h_flag = 0;
-    MC_HIP(hipMemcpyAsync(&h_flag, flag.ptr, 4, hipMemcpyDeviceToHost, s));
-    MC_HIP(hipStreamSynchronize(s));
-    MC_REQUIRE(!(h_flag & mc::kPPBadOffsets), MC_ERR_INVALID, "offsets must be ascending");
-    MC_REQUIRE(!(h_flag & mc::kPPBadIndex), MC_ERR_INVALID, "a point, mask or frame index is out of range");
-    MC_REQUIRE(!(h_flag & mc::kPPBadFrame), MC_ERR_INVALID,
-               "a mask's frame is not among the node's visible frames (post_process.py:69 IndexError)");
-    MC_REQUIRE(!(h_flag & mc::kPPTooWide), MC_ERR_UNSUPPORTED,
-               "a node spans more than 2^21 DBSCAN cells per axis (eps too small)");
-    std::vector<int64_t> h_npoff(N + 1, 0);
-    std::vector<int32_t> h_order(std::max(N, 1));
-    int64_t H = 0;
-    MC_HIP(hipMemcpyAsync(h_npoff.data(), a.npoff, static_cast<size_t>(N + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (N) MC_HIP(hipMemcpyAsync(h_order.data(), dorder.ptr, static_cast<size_t>(N) * 4, hipMemcpyDeviceToHost, s));
-    MC_HIP(hipMemcpyAsync(&H, hoff.as<int64_t>() + N, 8, hipMemcpyDeviceToHost, s));
-    MC_HIP(hipStreamSynchronize(s));
-
-    PPIn in;
-    in.P = a.P, in.E = a.E, in.Q = a.Q, in.H = H;
-    in.F = a.F, in.Mt = a.Mt, in.N = N;
-    in.scene.ptr = a.scene, in.pfm.ptr = a.pfm, in.moff.ptr = a.mask_off, in.mpts.ptr = a.mask_pts;
-    in.nvf.ptr = a.nvf, in.qfp.ptr = qfp.ptr, in.hoff.ptr = hoff.ptr, in.dorder.ptr = dorder.ptr;
-    in.h_npoff = h_npoff.data();
-    in.h_order = h_order.data();
-    pp_core(ctx, params, in, false);
-}
-
-int mc_pp_run_device(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points, int32_t num_frames,
-                     const double *scene_xyz, const uint64_t *pfm_bits, int32_t num_masks, const int64_t *mask_off,
-                     const int32_t *mask_pts, int32_t num_nodes, const uint64_t *node_vf_bits,
-                     const int64_t *node_pt_off, const int32_t *node_pts, const int64_t *node_mask_off,
-                     const int32_t *node_masks, const int32_t *node_mask_col)
-{
-    return guarded(ctx, [&] {
-        ctx->have_pp = false;
-        mc::PPArgs a{};
-        a.P = num_points, a.F = num_frames, a.Mt = num_masks, a.N = num_nodes;
-        a.scene = scene_xyz;
-        a.pfm = reinterpret_cast<const unsigned long long *>(pfm_bits);
-        a.nvf = reinterpret_cast<const unsigned long long *>(node_vf_bits);
-        a.mask_off = mask_off, a.npoff = node_pt_off, a.qoff = node_mask_off;
-        a.mask_pts = mask_pts, a.npts = node_pts, a.qm = node_masks, a.qcol = node_mask_col;
-        pp_run_device(ctx, params, a);
-    });
-}
-
-int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *scene_xyz, int scene_on_device)
-{
-    return guarded(ctx, [&] {
-        ctx->have_pp = false;
-        MC_REQUIRE(ctx->have_cluster, MC_ERR_STATE, "no clustering result (mc_cluster_run first)");
-        MC_REQUIRE(ctx->nodes_from_graph, MC_ERR_STATE, "the nodes were given by mc_nodes_set: no mask table");
-        MC_REQUIRE(!sharded(ctx) || ctx->sh_pending == 0, MC_ERR_STATE, "this rank does not hold the full result");
-        MC_REQUIRE(scene_xyz || (ctx->bp.have_points && ctx->bp.P == ctx->P), MC_ERR_STATE,
-                   "no scene points: pass scene_xyz or call mc_scene_set_points");
-        sync_stats(ctx);
-        hipStream_t s = ctx->stream;
-        const int K = ctx->K, N0 = ctx->N0, FW = ctx->FW, M = ctx->M, Min = ctx->M_in;
-        const int64_t P = ctx->P, np = ctx->h_stats[ST_NPTS];
-        DevBuf scene, moff, mlen, cnt, keepf, nid, dnn, sel, plen, qlen, inidx, nvf, qcol;
-        const double *d_scene = scene_xyz;
-        {
-            mc::TimedScope ts(ctx->timer, s, "pp_prep");
-            if (!scene_xyz) {  // the float32 points, widened exactly
-                scene.reserve(static_cast<size_t>(P) * 24 + 8);
-                hipLaunchKernelGGL(mc::k_pp_widen, grid_for(3 * P), dim3(256), 0, s, ctx->bp.scene.as<float>(), 3 * P,
-                                   scene.as<double>());
-                d_scene = scene.as<double>();
-            } else if (!scene_on_device) {
-                scene.reserve(static_cast<size_t>(P) * 24 + 8);
-                if (P) MC_HIP(hipMemcpyAsync(scene.ptr, scene_xyz, static_cast<size_t>(P) * 24, hipMemcpyHostToDevice, s));
-                d_scene = scene.as<double>();
-            }
-            // the mask table in input order: rows of skipped frames (not in the context's table) are empty
-            const int *d_inidx = nullptr;
-            if (M != Min) {
-                inidx.reserve(static_cast<size_t>(M) * 4 + 8);
-                if (M) MC_HIP(hipMemcpyAsync(inidx.ptr, ctx->h_in_index.data(), static_cast<size_t>(M) * 4, hipMemcpyHostToDevice, s));
-                d_inidx = inidx.as<int>();
-            }
-            mlen.reserve(static_cast<size_t>(Min) * 4 + 8);
-            moff.reserve(static_cast<size_t>(Min + 1) * 8);
-            MC_HIP(hipMemsetAsync(mlen.ptr, 0, static_cast<size_t>(Min) * 4 + 4, s));
-            if (M) hipLaunchKernelGGL(mc::k_pp_cl_masklen, grid_for(M), dim3(256), 0, s, M, d_inidx, ctx->d_mask_off.as<int>(),
-                                      mlen.as<int>());
-            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, mlen.as<int>(), Min, moff.as<int64_t>());
-            // nodes: the objects with at least 2 level-0 masks, in object order
-            cnt.reserve(static_cast<size_t>(K) * 4 + 8);
-            keepf.reserve(static_cast<size_t>(K) * 4 + 8);
-            nid.reserve(static_cast<size_t>(K + 1) * 4 + 8);
-            dnn.reserve(8);
-            MC_HIP(hipMemsetAsync(cnt.ptr, 0, static_cast<size_t>(K) * 4 + 4, s));
-            if (N0) hipLaunchKernelGGL(mc::k_pp_cl_count, grid_for(N0), dim3(256), 0, s, N0, ctx->d_final_label.as<int>(),
-                                       cnt.as<int>());
-            if (K) hipLaunchKernelGGL(mc::k_pp_cl_keep, grid_for(K), dim3(256), 0, s, K, cnt.as<int>(), keepf.as<int>());
-            mc::scan_device_n(s, keepf.as<int>(), nid.as<int>(), nullptr, K, dnn.as<int>());
-            MC_HIP(hipGetLastError());
-        }
-        int Nn = 0;
-        MC_HIP(hipMemcpyAsync(&Nn, dnn.ptr, 4, hipMemcpyDeviceToHost, s));
-        MC_HIP(hipStreamSynchronize(s));
-        MC_REQUIRE(Nn >= 0 && Nn <= K, MC_ERR_HIP, "node count out of range");
-        sel.reserve(static_cast<size_t>(Nn) * 4 + 8);
-        plen.reserve(static_cast<size_t>(Nn) * 4 + 8);
-        qlen.reserve(static_cast<size_t>(Nn) * 4 + 8);
-        nvf.reserve(static_cast<size_t>(Nn) * FW * 8 + 8);
-        qcol.reserve(static_cast<size_t>(N0) * 4 + 8);
-        ctx->d_pp_npoff.reserve(static_cast<size_t>(Nn + 1) * 8);
-        ctx->d_pp_qoff.reserve(static_cast<size_t>(Nn + 1) * 8);
-        ctx->d_pp_npts.reserve(static_cast<size_t>(np) * 4 + 8);
-        ctx->d_pp_qm.reserve(static_cast<size_t>(N0) * 4 + 8);
-        {
-            mc::TimedScope ts(ctx->timer, s, "pp_prep");
-            if (K) hipLaunchKernelGGL(mc::k_pp_cl_select, grid_for(K), dim3(256), 0, s, K, cnt.as<int>(), nid.as<int>(),
-                                      ctx->d_ptoff_out.as<int>(), sel.as<int>(), plen.as<int>(), qlen.as<int>());
-            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, plen.as<int>(), Nn, ctx->d_pp_npoff.as<int64_t>());
-            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, qlen.as<int>(), Nn, ctx->d_pp_qoff.as<int64_t>());
-            if (Nn) {
-                hipLaunchKernelGGL(mc::k_pp_cl_members, dim3(std::min(ceil_div(Nn, 4), 4096)), dim3(256), 0, s, Nn, N0,
-                                   sel.as<int>(), ctx->d_final_label.as<int>(), ctx->d_node0_g.as<int>(),
-                                   M != Min ? inidx.as<int>() : nullptr, ctx->d_mask_col.as<int>(),
-                                   ctx->d_pp_qoff.as<int64_t>(), ctx->d_pp_qm.as<int>(), qcol.as<int>());
-                hipLaunchKernelGGL(mc::k_pp_cl_gather, dim3(std::min(Nn, 4096)), dim3(256), 0, s, Nn, FW, sel.as<int>(),
-                                   ctx->d_ptoff_out.as<int>(), ctx->d_pts_out.as<int>(), ctx->fin_vf,
-                                   ctx->d_pp_npoff.as<int64_t>(), ctx->d_pp_npts.as<int>(), nvf.as<unsigned long long>());
-            }
-            MC_HIP(hipGetLastError());
-        }
-        mc::PPArgs a{};
-        a.P = P, a.F = ctx->F, a.Mt = Min, a.N = Nn;
-        a.scene = d_scene;
-        a.pfm = ctx->d_pfm.as<unsigned long long>();
-        a.nvf = nvf.as<unsigned long long>();
-        a.mask_off = moff.as<int64_t>(), a.npoff = ctx->d_pp_npoff.as<int64_t>(), a.qoff = ctx->d_pp_qoff.as<int64_t>();
-        a.mask_pts = ctx->d_mask_pts.as<int>(), a.npts = ctx->d_pp_npts.as<int>(), a.qm = ctx->d_pp_qm.as<int>();
-        a.qcol = qcol.as<int>();
-        pp_run_device(ctx, params, a);
-    });
-}
-
-// the export arrays of the last post-processing result, built once per result
-static void pp_build_export(mc_ctx *ctx)
-{
-    if (ctx->pp_export) return;
-    hipStream_t s = ctx->stream;
-    const int K = ctx->pp_info.num_objects, nf = ctx->pp_info.num_final;
-    const int64_t np = ctx->pp_opoff[nf], nm = ctx->pp_omoff[nf];
-    auto up = [&](DevBuf &b, const void *h, size_t bytes) {
-        b.reserve(bytes + 8);
-        if (bytes) MC_HIP(hipMemcpyAsync(b.ptr, h, bytes, hipMemcpyHostToDevice, s));
-    };
-    up(ctx->d_pp_fslot, ctx->pp_fslot.data(), static_cast<size_t>(K) * 4);
-    up(ctx->d_pp_finobj, ctx->pp_fin.data(), static_cast<size_t>(nf) * 4);
-    up(ctx->d_pp_finnode, ctx->pp_fin_node.data(), static_cast<size_t>(nf) * 4);
-    up(ctx->d_pp_opoff, ctx->pp_opoff.data(), static_cast<size_t>(nf + 1) * 8);
-    up(ctx->d_pp_omoff, ctx->pp_omoff.data(), static_cast<size_t>(nf + 1) * 8);
-    ctx->d_pp_opts.reserve(np * 4 + 8);
-    ctx->d_pp_omask.reserve(nm * 4 + 8);
-    ctx->d_pp_ocov.reserve(nm * 8 + 8);
-    ctx->d_pp_repre.reserve(static_cast<size_t>(nf) * 20 + 8);
-    if (nf) {
-        mc::TimedScope ts(ctx->timer, s, "pp_export");
-        hipLaunchKernelGGL(mc::k_pp_ex_fill, dim3(std::min(nf, 4096)), dim3(256), 0, s, nf, ctx->d_pp_finobj.as<int>(),
-                           ctx->d_pp_finnode.as<int>(), ctx->d_pp_npoff.as<int64_t>(), ctx->d_pp_npts.as<int>(),
-                           ctx->d_pp_eobj.as<int>(), ctx->d_pp_qoff.as<int64_t>(), ctx->d_pp_qm.as<int>(),
-                           ctx->d_pp_qobj.as<int>(), ctx->d_pp_qcov.as<double>(), ctx->d_pp_opoff.as<int64_t>(),
-                           ctx->d_pp_opts.as<int>(), ctx->d_pp_omoff.as<int64_t>(), ctx->d_pp_omask.as<int>(),
-                           ctx->d_pp_ocov.as<double>());
-        hipLaunchKernelGGL(mc::k_pp_ex_repre, dim3(std::min(ceil_div(nf, 4), 4096)), dim3(256), 0, s, nf,
-                           ctx->d_pp_omoff.as<int64_t>(), ctx->d_pp_ocov.as<double>(), ctx->d_pp_repre.as<int>());
-        MC_HIP(hipGetLastError());
-    }
-    MC_HIP(hipStreamSynchronize(s));  // the uploads read the context's host vectors
-    ctx->timer.collect();
-    ctx->pp_export = true;
-}
-
-int mc_pp_export_info(mc_ctx *ctx, int32_t *num_final, int64_t *num_points, int64_t *num_masks)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        const int nf = ctx->pp_info.num_final;
-        if (num_final) *num_final = nf;
-        if (num_points) *num_points = ctx->pp_opoff[nf];
-        if (num_masks) *num_masks = ctx->pp_omoff[nf];
-    });
-}
-
-int mc_pp_export(mc_ctx *ctx, int64_t *obj_pt_off, int32_t *obj_pts, int64_t *obj_mask_off, int32_t *obj_masks,
-                 double *obj_mask_cov, int32_t *obj_repre, int32_t *obj_node, int on_device)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        pp_build_export(ctx);
-        hipStream_t s = ctx->stream;
-        const int nf = ctx->pp_info.num_final;
-        const int64_t np = ctx->pp_opoff[nf], nm = ctx->pp_omoff[nf];
-        auto cp = [&](void *dst, const DevBuf &src, size_t bytes) {
-            if (dst && bytes)
-                MC_HIP(hipMemcpyAsync(dst, src.ptr, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        };
-        cp(obj_pt_off, ctx->d_pp_opoff, static_cast<size_t>(nf + 1) * 8);
-        cp(obj_pts, ctx->d_pp_opts, static_cast<size_t>(np) * 4);
-        cp(obj_mask_off, ctx->d_pp_omoff, static_cast<size_t>(nf + 1) * 8);
-        cp(obj_masks, ctx->d_pp_omask, static_cast<size_t>(nm) * 4);
-        cp(obj_mask_cov, ctx->d_pp_ocov, static_cast<size_t>(nm) * 8);
-        cp(obj_repre, ctx->d_pp_repre, static_cast<size_t>(nf) * 20);
-        cp(obj_node, ctx->d_pp_finnode, static_cast<size_t>(nf) * 4);
-        MC_HIP(hipStreamSynchronize(s));
-    });
-}
-
-int mc_pp_export_pred_masks(mc_ctx *ctx, uint8_t *out, int on_device)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        pp_build_export(ctx);
-        hipStream_t s = ctx->stream;
-        const int nf = ctx->pp_info.num_final;
-        const int64_t P = ctx->pp_P, E = ctx->pp_info.num_entries;
-        const size_t bytes = static_cast<size_t>(P) * nf;
-        if (!bytes) return;
-        MC_REQUIRE(out, MC_ERR_INVALID, "null argument");
-        DevBuf tmp;
-        uint8_t *d = out;
-        if (!on_device) {
-            tmp.reserve(bytes);
-            d = tmp.as<uint8_t>();
-        }
-        MC_HIP(hipMemsetAsync(d, 0, bytes, s));
-        {
-            mc::TimedScope ts(ctx->timer, s, "pp_export");
-            hipLaunchKernelGGL(mc::k_pp_ex_pred, grid_for(E), dim3(256), 0, s, E, ctx->d_pp_npts.as<int>(),
-                               ctx->d_pp_eobj.as<int>(), ctx->d_pp_fslot.as<int>(), nf, d);
-            MC_HIP(hipGetLastError());
-        }
-        if (!on_device) MC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, s));
-        MC_HIP(hipStreamSynchronize(s));
-        ctx->timer.collect();
-    });
-}
-
-int mc_pp_get_info(mc_ctx *ctx, mc_pp_info *info)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        MC_REQUIRE(info, MC_ERR_INVALID, "null argument");
-        *info = ctx->pp_info;
-    });
-}
-
-int mc_pp_get_results(mc_ctx *ctx, int32_t *entry_object, int32_t *mask_object, double *mask_coverage,
-                      uint8_t *object_state, int32_t *object_node, double *object_bbox)
-{
-    return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        if (entry_object || mask_object || mask_coverage) pp_fetch_host(ctx);
-        auto cp = [](void *dst, const void *src, size_t bytes) {
-            if (dst && bytes) std::memcpy(dst, src, bytes);
-        };
-        cp(entry_object, ctx->pp_entry_obj.data(), ctx->pp_entry_obj.size() * 4);
-        cp(mask_object, ctx->pp_qobj.data(), ctx->pp_qobj.size() * 4);
-        cp(mask_coverage, ctx->pp_qcov.data(), ctx->pp_qcov.size() * 8);
-        cp(object_state, ctx->pp_state.data(), ctx->pp_state.size());
-        cp(object_node, ctx->pp_obj_node.data(), ctx->pp_obj_node.size() * 4);
-        cp(object_bbox, ctx->pp_box.data(), ctx->pp_box.size() * 8);
-    });
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // instance-evaluation match counts (evaluation/evaluate.py:254-329)

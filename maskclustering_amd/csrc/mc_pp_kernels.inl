@@ -659,8 +659,8 @@ __global__ __launch_bounds__(1024) void k_pp_greedy(int K, const unsigned char *
 }
 
 // ---------------------------------------------------------------------------------------------
-// device-resident entries (mc_pp_run_device, mc_pp_run_clustered): the checks and the per-node
-// layout mc_pp_run does on the host, the node arrays of the clustered objects, the export
+// the checks of the argument arrays and the per-node layout of all three entries (pp_layout,
+// mc_pp_host.inl), the node arrays of the clustered objects (mc_pp_run_clustered), the export
 // ---------------------------------------------------------------------------------------------
 // the argument arrays of mc_pp_run, as device pointers
 struct PPArgs {

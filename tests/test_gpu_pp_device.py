@@ -1,7 +1,12 @@
 """Device-resident post-processing and export (mc_pp_run_device, mc_pp_run_clustered, mc_pp_export,
 mc_pp_export_pred_masks) against mc_pp_run, the Python rebuild of the drop-in and the CPU
 restatement (oracle/pp_oracle.py).  Bit-exact: info, every result array, point and mask lists,
-coverages (float64), representative masks, the prediction matrix."""
+coverages (float64), representative masks, the prediction matrix.
+
+mc_pp_run uploads its arrays and takes the device entry's path (k_pp_validate, k_pp_prep, k_pp_order), so
+the entry-against-entry tests below pin the upload; the independent check of those kernels is
+test_gpu_pp.py, which compares mc_pp_run with the reference's goldens and the oracle, the
+MC_PP_BIG_MIN=60 and MC_PP_GREEDY_CAP=0 cases included."""
 import functools
 from types import SimpleNamespace
 
@@ -316,21 +321,6 @@ def test_states_and_errors():
     ok = _small_args()
     _run_device(ctx, _params(0.0), ok)
     assert ctx.pp_info().num_final == 1 and ctx.pp_export()["obj_pts"].tolist() == [0, 1, 2, 3]
-    with pytest.raises(_native.McError) as e:
-        _run_device(ctx, _params(0.0), _small_args(vf=(1, 0, 0, 0)))  # frame 1 not visible (:69)
-    assert e.value.code == _native.MC_ERR_INVALID
-    with pytest.raises(_native.McError) as e:
-        _run_device(ctx, _params(0.0, eps=1e-7), ok)                  # 5 / 1.01e-7 cells > 2^21
-    assert e.value.code == _native.MC_ERR_UNSUPPORTED
-    bad = dict(ok, pts=ok["pts"].copy())
-    bad["pts"][2] = 5                                                 # node point out of [0, P)
-    with pytest.raises(_native.McError) as e:
-        _run_device(ctx, _params(0.0), bad)
-    assert e.value.code == _native.MC_ERR_INVALID
-    bad = dict(ok, qm=np.array([0, 2], np.int32))                     # mask row out of the table
-    with pytest.raises(_native.McError) as e:
-        _run_device(ctx, _params(0.0), bad)
-    assert e.value.code == _native.MC_ERR_INVALID
 
     def empty():
         r = ctx.pp_export()
@@ -339,11 +329,39 @@ def test_states_and_errors():
         assert all(len(r[k]) == 0 for k in ("obj_pts", "obj_masks", "obj_mask_cov", "obj_node"))
         assert r["obj_repre"].shape == (0, 5)
         assert ctx.pp_pred_masks(5).shape == (5, 0) and tuple(ctx.pp_pred_masks(5, device=True).shape) == (5, 0)
-    none = dict(ok, vf=ok["vf"][:0], poff=ok["poff"][:1], pts=ok["pts"][:0], qoff=ok["qoff"][:1], qm=ok["qm"][:0],
-                qc=ok["qc"][:0])
-    _run_device(ctx, _params(0.0), none)                              # empty node list
-    assert ctx.pp_info().num_objects == 0
-    empty()
-    _run_device(ctx, _params(1.0), ok)                                # no ratio is above 1: every object filtered out
-    assert ctx.pp_info().num_objects > 0
-    empty()
+
+    for run in (_run_device, _run_host):                                  # the same checks behind both entries
+        with pytest.raises(_native.McError) as e:
+            run(ctx, _params(0.0), _small_args(vf=(1, 0, 0, 0)))          # frame 1 not visible (:69)
+        assert e.value.code == _native.MC_ERR_INVALID
+        with pytest.raises(_native.McError) as e:
+            run(ctx, _params(0.0, eps=1e-7), ok)                          # 5 / 1.01e-7 cells > 2^21
+        assert e.value.code == _native.MC_ERR_UNSUPPORTED
+        bad = dict(ok, pts=ok["pts"].copy())
+        bad["pts"][2] = 5                                                 # node point out of [0, P)
+        with pytest.raises(_native.McError) as e:
+            run(ctx, _params(0.0), bad)
+        assert e.value.code == _native.MC_ERR_INVALID
+        bad = dict(ok, qm=np.array([0, 2], np.int32))                     # mask row out of the table
+        with pytest.raises(_native.McError) as e:
+            run(ctx, _params(0.0), bad)
+        assert e.value.code == _native.MC_ERR_INVALID
+        assert ok["moff"].tolist() == [0, 4, 7]
+        bad = dict(ok, moff=np.array([0, 8, 7], np.int64))                # mask offsets: interior entry above the last
+        with pytest.raises(_native.McError) as e:
+            run(ctx, _params(0.0), bad)
+        assert e.value.code == _native.MC_ERR_INVALID
+        with pytest.raises(_native.McError) as e:
+            ctx.pp_info()                                                 # the failed call left no result
+        assert e.value.code == _native.MC_ERR_STATE
+        run(ctx, _params(0.0), ok)                                        # a good call on the same context
+        assert ctx.pp_info().num_final == 1 and ctx.pp_export()["obj_pts"].tolist() == [0, 1, 2, 3]
+
+        none = dict(ok, vf=ok["vf"][:0], poff=ok["poff"][:1], pts=ok["pts"][:0], qoff=ok["qoff"][:1], qm=ok["qm"][:0],
+                    qc=ok["qc"][:0])
+        run(ctx, _params(0.0), none)                                      # empty node list
+        assert ctx.pp_info().num_objects == 0
+        empty()
+        run(ctx, _params(1.0), ok)                                        # no ratio is above 1: every object filtered out
+        assert ctx.pp_info().num_objects > 0
+        empty()
