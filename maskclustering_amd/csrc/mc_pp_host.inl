@@ -535,7 +535,7 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
                                    M != Min ? inidx.as<int>() : nullptr, ctx->d_mask_col.as<int>(),
                                    ctx->d_pp_qoff.as<int64_t>(), ctx->d_pp_qm.as<int>(), qcol.as<int>());
                 hipLaunchKernelGGL(mc::k_pp_cl_gather, dim3(std::min(Nn, 4096)), dim3(256), 0, s, Nn, FW, sel.as<int>(),
-                                   ctx->d_ptoff_out.as<int>(), ctx->d_pts_out.as<int>(), ctx->fin_vf,
+                                   ctx->d_ptoff_out.as<int>(), ctx->d_pts_out.as<int>(), ctx->fin.vf,
                                    ctx->d_pp_npoff.as<int64_t>(), ctx->d_pp_npts.as<int>(), nvf.as<unsigned long long>());
             }
             MC_HIP(hipGetLastError());

@@ -13,11 +13,11 @@ import json
 import os
 import sys
 
-# timed group of mc_api.hip (TimedScope names) -> (kernel-name prefixes, anchor prefixes): a group
+# timed group of the host drivers, mc_*_host.inl (TimedScope names) -> (kernel-name prefixes, anchor prefixes): a group
 # launch is one launch of an anchor kernel (TimedScope count), and its bytes are the total bytes of
 # all the group's kernels over the anchor launches.  An anchor must launch exactly once per timed
 # scope: k_bp_vox_order launches twice per batch (once in bp_voxel's scope, once in bp_denoise's,
-# mc_api.hip), so bp_voxel anchors on its first LDS tier and SHARED splits vox_order between the two.
+# mc_bp_host.inl), so bp_voxel anchors on its first LDS tier and SHARED splits vox_order between the two.
 SHARED = {"mc::k_bp_vox_order": {"bp_voxel": 0.5, "bp_denoise": 0.5}}
 GROUPS = {
     "s3_masks": (["mc::k_s3_masks"], ["mc::k_s3_masks<1>"]),

@@ -102,7 +102,7 @@ class OracleShardCtx:
         self.M = M = L.orcs_s2(P, F, M_in, self.col, self.off, self.pts, kept, self.bnd, pt_off, pt_ent)
         self.kept = kept[:M_in]
         gidx = np.where(self.kept > 0, np.cumsum(self.kept) - 1, -1).astype(np.int32)
-        # contiguous row blocks of about equal point counts (mc_api.hip build_s3_lists)
+        # contiguous row blocks of about equal point counts (mc_graph_plan.hpp shard_row_cut)
         h_off = np.zeros(M + 1, np.int64)
         np.cumsum(np.diff(self.off)[self.kept > 0], out=h_off[1:])
         tot, W = int(h_off[-1]), self.world

@@ -162,6 +162,34 @@ def test_synthetic_scene_vs_oracle(run, shape, seed, cfg):
     assert_matches(got, want)
 
 
+@pytest.mark.parametrize("n", [8, 9])
+def test_point_in_many_objects_s7_paths(run, n):
+    """S7 builds the objects' point ranges per point while no point lies in more than 8 objects, and
+    per node otherwise.  n solo masks (one per frame, 40 own points each) share point 0 and stay n
+    objects; a mask of 60 other points seen in frames 0 and 1 gives the observer pair the thresholds
+    need.  n = 8: the per-point path at its limit (9 objects); n = 9: the per-node fallback (10)."""
+    from maskclustering_amd.synthetic import SceneMasks
+    from oracle import oracle
+    S = 40
+    P = 1 + n * S + 60
+    frames = []
+    for i in range(n):
+        fl = [(1, np.concatenate([[0], np.arange(1 + i * S, 1 + (i + 1) * S)]))]
+        if i < 2:
+            fl.append((2, np.arange(P - 60, P)))
+        frames.append(fl)
+    s = SceneMasks.from_frame_lists(P, frames)
+    mvt, ust, ct, cont = 0.3, 0.3, 0.9, 0.8
+    want = oracle.run(s.num_points, s.num_frames, s.mask_col, s.mask_label, s.mask_off, s.mask_pts, mvt, ust, ct, cont)
+    off, idx = np.asarray(want["obj_pt_off"]), np.asarray(want["obj_pt_idx"])
+    assert P == {8: 381, 9: 421}[n] and len(off) - 1 == n + 1
+    assert sum(0 in idx[off[k]:off[k + 1]] for k in range(len(off) - 1)) == n  # the case stays on its branch
+    inp = dict(num_points=s.num_points, num_frames=s.num_frames, mask_col=s.mask_col, mask_label=s.mask_label,
+               mask_off=s.mask_off, mask_pts=s.mask_pts, mask_visible_threshold=mvt,
+               undersegment_filter_threshold=ust, view_consensus_threshold=ct, contained_threshold=cont)
+    assert_matches(_run_case(run, inp), want)
+
+
 def test_repeat_is_deterministic(run):
     from maskclustering_amd.synthetic import make_shape
     s = make_shape("c1", seed=5)
