@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "mc_internal.hpp"
+#include "mc_bp_nbpack.hpp"
 #include "mc_bp_plan.hpp"
 #include "mc_graph_plan.hpp"
 #include "mc_pp_plan.hpp"

@@ -1458,14 +1458,65 @@ __device__ __forceinline__ unsigned nb_class(double d2, const BpDev &pr)
     return 3u - (d2 < pr.knn_r2[0] ? 1u : 0u) - (d2 < pr.knn_r2[1] ? 1u : 0u) - (d2 < pr.knn_r2[2] ? 1u : 0u);
 }
 
-// The eps-neighbour list of sorted position q (point a, cell (x, y, z)): every point of the 27 cells
-// with d2 < eps2 (self included), in cell-walk order.  One predicate per candidate (cell key and
-// distance together, the record loaded whole) and one store; entries past kBpNbCap overwrite the
-// last slot (the list is unused then: the point walks its cells).  Returns the count.
+// The list builders' walk over the records of ranges d0 .. 26 (range(d, key): the bucket range of
+// cell d and its key), flat: a lane goes through the records of its non-empty ranges in one loop,
+// two per trip, and takes its next range in the trip that finishes the last one (that range was read
+// while the last one's records were scanned).  A wave holds points of several cells (consecutive
+// positions of the hash order) whose neighbourhoods are filled differently: a loop per cell runs
+// every cell for the lane with the most records in that cell, the flat loop for the lane with the
+// most records in all (C3 and C2 denoise -3 %, docs/experiments.md "own-walk lists").
+// visit(record, position, key) tests one record; the key ~0, which no record has, masks the second
+// record of a trip past the range's end.
+template <typename Range, typename Visit>
+__device__ __forceinline__ void lds_flat_walk(const BpLdsGrid &g, int d0, Range &&range, Visit &&visit)
+{
+    unsigned cells = 0;  // bit d: range d holds records
+#pragma unroll 3
+    for (int d = d0; d < 27; d++) {
+        unsigned long long k;
+        const int2 r = range(d, k);
+        cells |= (r.y > r.x ? 1u : 0u) << d;
+    }
+    auto next = [&](unsigned long long &k) {  // the next non-empty range ({0, 0}: none left)
+        if (!cells) return make_int2(0, 0);
+        const int d = __ffs(static_cast<int>(cells)) - 1;
+        cells &= cells - 1;
+        return range(d, k);
+    };
+    unsigned long long key = 0, nkey = 0;
+    int2 nr = next(nkey);
+    int q2 = 0, e = 0;
+#pragma unroll 1
+    while (true) {
+        if (q2 >= e) {
+            if (nr.x >= nr.y) break;
+            key = nkey;
+            q2 = nr.x;
+            e = nr.y;
+            nr = next(nkey);
+        }
+        const double4 p0 = g.pt[q2], p1 = g.pt[min(q2 + 1, e - 1)];
+        visit(p0, q2, key);
+        visit(p1, q2 + 1, q2 + 1 < e ? key : ~0ull);
+        q2 += 2;
+    }
+}
+
+// The eps-neighbour list of sorted position q (point a, cell (x, y, z)), built by the lane that owns
+// q (the classes whose counts live in global scratch): every point of the 27 cells with d2 < eps2
+// (self included), in cell-walk order.  One predicate per candidate (cell key and distance together,
+// the record loaded whole).  The entries are packed in registers (mc::NbPack, mc_bp_nbpack.hpp) and
+// leave as whole 16-byte words: one store per eight entries, and the last, partial word after the
+// walk with its unused half-words zero.  Entries past kBpNbCap are counted and not stored (the list
+// is unused then: the point walks its cells).  farA / farB: the last neighbour of radius class 3 / 2
+// (the union's sampled links, step 6).  Returns the count.
+// (Measured and not kept, docs/experiments.md "own-walk lists": this builder in the 512 .. 3072
+// classes instead of the pair pass: C3 denoise +15 %, C2 +11 %; it tests twice the candidates, and
+// the pair pass's LDS atomics and 2-byte stores cost less than those tests.)
 template <int N>
-__device__ __forceinline__ int lds_eps_list(const BpLdsGrid &g, int x, int y, int z, double ax, double ay, double az,
-                                            const BpDev &pr, unsigned short *__restrict__ nbw, int q, int &farA,
-                                            int &farB)
+__device__ __forceinline__ int lds_eps_own(const BpLdsGrid &g, int x, int y, int z, double ax, double ay, double az,
+                                           const BpDev &pr, unsigned short *__restrict__ nbw, int q, int &farA,
+                                           int &farB)
 {
     auto range = [&](int d, unsigned long long &key) {
         const int cx = x + d % 3 - 1, cy = y + (d / 3) % 3 - 1, cz = z + d / 9 - 1;
@@ -1475,35 +1526,36 @@ __device__ __forceinline__ int lds_eps_list(const BpLdsGrid &g, int x, int y, in
         const unsigned b = mod_mul(bp_hash3(cx, cy, cz), g.nb);
         return make_int2(g.bs[b], g.bs[b + 1]);
     };
+    // word u of q's list: byte (u * N + q) * 16 of the region (a 32-bit offset, < 128 * N <= 2^21: a
+    // store with the workgroup's region base in SGPRs and one VGPR offset, no 64-bit address arithmetic)
+    auto put = [&](const mc::NbPack &acc, int cnt) {
+        const unsigned off =
+            (static_cast<unsigned>(mc::nb_store_word(cnt)) * static_cast<unsigned>(N) + static_cast<unsigned>(q)) * 16u;
+        *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(nbw) + off) = make_uint4(acc.a0, acc.a1, acc.a2, acc.a3);
+    };
     const double eps2 = pr.eps2;
     int cnt = 0;
+    int fa = farA, fb = farB;  // locals, selected: written through the references they live in scratch
+    mc::NbPack acc;
     auto visit = [&](const double4 &p, int q2, unsigned long long key) {
         const double dx = ax - p.x, dy = ay - p.y, dz = az - p.z;
         const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
         if (static_cast<unsigned long long>(__double_as_longlong(p.w)) == key && d2 < eps2) {  // (no kept bits yet)
             const unsigned c = nb_class(d2, pr);
-            nb_put<N>(nbw, q, min(cnt, kBpNbCap - 1), static_cast<unsigned>(q2) | (c << 14));
-            if (c == 3u) farA = q2;  // far neighbours: the sampled links of the union (step 6)
-            if (c == 2u) farB = q2;
+            acc.push(static_cast<unsigned>(q2) | (c << 14));
+            fa = c == 3u ? q2 : fa;
+            fb = c == 2u ? q2 : fb;
             cnt++;
+            if (mc::nb_store_full(cnt, kBpNbCap)) put(acc, cnt);
         }
     };
-    unsigned long long nkey = 0;
-    int2 nr = range(0, nkey);
-#pragma unroll 1
-    for (int d = 0; d < 27; d++) {
-        const unsigned long long key = nkey;
-        const int2 r = nr;
-        if (d + 1 < 27) nr = range(d + 1, nkey);
-        int q2 = r.x;
-        const int e = r.y;
-        for (; q2 + 2 <= e; q2 += 2) {
-            const double4 p0 = g.pt[q2], p1 = g.pt[q2 + 1];
-            visit(p0, q2, key);
-            visit(p1, q2 + 1, key);
-        }
-        if (q2 < e) visit(g.pt[q2], q2, key);
+    lds_flat_walk(g, 0, range, visit);
+    if (mc::nb_store_tail(cnt, kBpNbCap)) {
+        acc.flush(cnt & (mc::kNbWordSlots - 1));
+        put(acc, cnt);
     }
+    farA = fa;
+    farB = fb;
     return cnt;
 }
 
@@ -1511,7 +1563,7 @@ __device__ __forceinline__ int lds_eps_list(const BpLdsGrid &g, int x, int y, in
 // position q visits half of its own bucket cyclically and the 13 cells after its own in (z, y, x)
 // order; a pair within eps is appended to both lists, each at the slot an LDS atomic on its counter
 // returns (sflag[] holds the counts, self entries already in slot 0).  Half the candidate records of
-// lds_eps_list; the slot order within a list is arbitrary, which no consumer depends on (the union
+// lds_eps_own; the slot order within a list is arbitrary, which no consumer depends on (the union
 // and the border labels are order-free, the k-NN sorts).  Own bucket [s, e) of c positions: q
 // visits the next h positions cyclically, h = (c - 1) / 2, plus the opposite one when c is even and
 // q is in the first half, so every pair of the bucket is visited once and each point's first list
@@ -1548,7 +1600,7 @@ __device__ __forceinline__ void lds_eps_pairs(const BpLdsGrid &g, int x, int y, 
             // both slots' atomics in flight together; the radius class and the far links (radius
             // classes 3 and 2 of this point's forward walk: the union's sampled links, step 6, stored
             // once after the walk) computed under them; one wait before the stores.  Entries past
-            // the cap overwrite the last slot (as lds_eps_list): every slot still holds a neighbour,
+            // the cap overwrite the last slot: every slot still holds a neighbour,
             // and a list past the cap is not read (its point walks the cells), so no branch
             const int o1 = atomicAdd(&sflag[q], 1), o2 = atomicAdd(&sflag[q2], 1);
             const unsigned c = nb_class(d2, pr) << 14;
@@ -1559,27 +1611,15 @@ __device__ __forceinline__ void lds_eps_pairs(const BpLdsGrid &g, int x, int y, 
             nb_put<N>(nbw, q2, min(o2, kBpNbCap - 1), static_cast<unsigned>(q) | c);
         }
     };
-    unsigned long long nkey = 0;
-    int2 nr = range(12, nkey);
-#pragma unroll 1
-    for (int d = 12; d < 27; d++) {
-        const unsigned long long key = nkey;
-        const int2 r = nr;
-        if (d + 1 < 27) nr = range(d + 1, nkey);
-        int q2 = r.x;
-        const int e = r.y;
-        for (; q2 + 2 <= e; q2 += 2) {
-            const double4 p0 = g.pt[q2], p1 = g.pt[q2 + 1];
-            visit(p0, q2, key);
-            visit(p1, q2 + 1, key);
-        }
-        if (q2 < e) visit(g.pt[q2], q2, key);
-    }
+    lds_flat_walk(g, 12, range, visit);
     farA[q] = fa;
     farB[q] = fb;
 }
 
-// the uint4 words of sorted position q's first cnt slots, all issued together; the others zero
+// the uint4 words of sorted position q's first cnt slots, all issued together; the others zero.
+// The caller must be the lane that owns q in the list phase (q = t + k * T, as every loop over q in
+// k_bp_denoise_lds): lds_eps_own's lists are handed over by program order only, so a reader that takes
+// q any other way needs a sync_global() after step 5 first.
 template <int N>
 __device__ __forceinline__ void nb_load(const unsigned short *__restrict__ nbw, int q, int cnt, unsigned (&w)[32])
 {
@@ -1598,7 +1638,7 @@ __device__ __forceinline__ void nb_load(const unsigned short *__restrict__ nbw, 
 // slot k of the loaded words (k must be wave-uniform: register-relative moves, no scratch)
 __device__ __forceinline__ unsigned nb_ent(const unsigned (&w)[32], int k)
 {
-    return (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+    return nb_slot(w, k);  // mc_bp_nbpack.hpp
 }
 
 // fn(k, entry, pre(entry)) for slots 0 .. cnt - 1; pre(entry of the next slot) is issued before fn
@@ -1954,12 +1994,17 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
             }
             sync_global();  // the lists hold other waves' stores
         } else {
+            // (hand-off: the list of q is stored only by the lane that owns q, q = t + k * T, and
+            // every reader takes q from a loop of the same shape (the sampled links and the union of
+            // step 6, the labels of step 8, the k-NN list pass of step 10, the diagnostics' list
+            // check), so a list is read by the lane that stored it, in program order; the counts and
+            // far links are read by other lanes after the barrier below, a sync_global() here)
             for (int q = t; q < n; q += T) {
                 int x, y, z;
                 unpack3(keyof(q), x, y, z);
                 const double ax = spt[q].x, ay = spt[q].y, az = spt[q].z;
                 int fa = q, fb = q;
-                sflag[q] = lds_eps_list<N>(g, x, y, z, ax, ay, az, pr, nbw, q, fa, fb);
+                sflag[q] = lds_eps_own<N>(g, x, y, z, ax, ay, az, pr, nbw, q, fa, fb);
                 spar[q] = q;
                 sX[q] = fa;
                 slab[q] = fb;
@@ -1983,7 +2028,12 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
         if (t == 0) s_ndef = 0;
         for (int q = t; q < n; q += T) {
             if (nb_cnt(sflag[q]) < pr.minpts) continue;
-            const uint4 w0 = reinterpret_cast<const uint4 *>(nbw)[q];  // slots 0..7 (slot 0: self in pair lists)
+            // slots 0..7; slot 1 is the first sampled link: the first neighbour of a pair list (slot 0 is
+            // self there), the second entry in walk order of an own-walk list (which may be self: skipped
+            // below).  A core point has cnt >= minpts entries, so slot 1 is a stored entry only for
+            // minpts >= 2 (DBSCAN's 4 here): with minpts 1 a one-entry own-walk list would give its zero
+            // padding, position 0, and a pair list a stale slot
+            const uint4 w0 = reinterpret_cast<const uint4 *>(nbw)[q];
             const int cand[3] = {static_cast<int>(((w0.x >> 16) & 0xFFFFu) & kNbPos), sX[q], slab[q]};
 #pragma unroll
             for (int r = 0; r < 3; r++) {
