@@ -429,6 +429,51 @@ int mc_ev_ap(mc_ctx *ctx, double *ap /* C*O */, int64_t *stats /* C*O*4 */);
 int mc_ev_get_curve(mc_ctx *ctx, int32_t class_index, int32_t overlap_index, int64_t *num_scores, double *scores,
                     int64_t *tp, int64_t *fp, int64_t *fn);
 
+/* ---- the accumulation as a state buffer: export and merge ---------------------------------------
+ * AP depends only on each (class, overlap) cell's multiset of (score, true) examples, its hard
+ * false negative count and its has_gt / has_pred flags.  The state buffer holds exactly that, per
+ * cell as runs: the distinct scores ascending, each with its count of true and of false examples.
+ * It is how per-rank accumulations of a scene-parallel sweep reach one rank (sweep.py) and how a
+ * long sweep is checkpointed.
+ *
+ * The buffer is one contiguous little-endian run of 8-byte-aligned sections (4-byte sections are
+ * padded with zeros to a multiple of 8 bytes); cell = class_index * O + overlap_index:
+ *   header     int64 [6]       (version << 32) | 0x5645434d ("MCEV"; version 1), C, O,
+ *                              min_region_size, no_class (0 / 1), R = runs of all cells
+ *   class_ids  int32 [C]       as given to mc_ev_begin
+ *   overlaps   double [O]      as given to mc_ev_begin
+ *   run_off    int64 [C*O + 1] cell c's runs are run_off[c] .. run_off[c + 1]; from 0 ascending to R
+ *   hard_fn    int64 [C*O]
+ *   flags      uint32 [C*O]    has_gt | has_pred << 1
+ *   key        uint64 [R]      the score as a sortable key: for the double's bits b (-0.0 taken as
+ *                              0.0), ~b if b's sign bit is set, else b | 1 << 63; strictly ascending
+ *                              within a cell
+ *   n_true     uint32 [R]      the run's true examples
+ *   n_false    uint32 [R]      its false examples; n_true + n_false >= 1
+ * The form is canonical: accumulations with the same multisets, counts and flags export the same
+ * bytes, whatever order and grouping their scans arrived in.
+ *
+ * mc_ev_state_info: the runs, the examples and the buffer's size in bytes (an accumulation without
+ * scans: 0 runs).  mc_ev_state_export: the buffer to buf (a device pointer with on_device);
+ * MC_ERR_INVALID if bytes is below mc_ev_state_info's.  The runs are computed once and kept until
+ * the accumulation changes; neither call changes the accumulation or the last scan's tables.
+ *
+ * mc_ev_state_merge adds a buffer's examples, hard false negatives (sum) and flags (OR) to the
+ * accumulation, as if the buffer's scans had been added to this context; it is no scan
+ * (mc_ev_scan_info / mc_ev_get_scan are unchanged).  bytes may exceed the buffer's size (a padded
+ * transport buffer); a device buffer must be 8-byte aligned.  The header's sizes are checked against
+ * bytes before anything is sized from them; of a device buffer only the header and the per-cell
+ * sections come to the host, the runs are checked by a kernel behind one flag word.
+ * MC_ERR_INVALID: another configuration than mc_ev_begin's (C, O, class ids in order, overlaps bit
+ * for bit, min_region_size, no_class) or a malformed buffer (magic, truncated, offsets not from 0
+ * ascending to R, keys not strictly ascending within a cell, a key no score has (NaN), a run
+ * without examples, a negative hard_fn, unknown flag bits).  MC_ERR_UNSUPPORTED: the accumulation
+ * would reach 2^31 examples.  All checks precede the first write: an error leaves the accumulation
+ * as it was. */
+int mc_ev_state_info(mc_ctx *ctx, int64_t *num_runs, int64_t *num_examples, int64_t *bytes);
+int mc_ev_state_export(mc_ctx *ctx, void *buf, int64_t bytes, int on_device);
+int mc_ev_state_merge(mc_ctx *ctx, const void *buf, int64_t bytes, int on_device);
+
 /* ---- frame decode -------------------------------------------------------
  * Replaces the per-frame host work of dataset/scannet.py:49-54 (get_depth: uint16 / depth_scale
  * as float64, stored float32; matterport.py:92 and scannetpp.py:169 alike) and :68-73

@@ -43,7 +43,7 @@ EXPORTED = [
     "mc_setorder_begin", "mc_setorder_finish", "mc_setorder_free",
     "mc_comm_unique_id", "mc_ctx_comm_init", "mc_ctx_attach_comm",
     "mc_ev_begin", "mc_ev_add_scan", "mc_ev_add_scan_clustered", "mc_ev_add_matches", "mc_ev_scan_info", "mc_ev_get_scan",
-    "mc_ev_ap", "mc_ev_get_curve",
+    "mc_ev_ap", "mc_ev_get_curve", "mc_ev_state_info", "mc_ev_state_export", "mc_ev_state_merge",
 ]
 MC_COMM_ID_BYTES = 128
 
@@ -206,6 +206,9 @@ def load():
         "mc_ev_get_scan": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mc_ev_ap": (ctypes.c_int, [vp, vp, vp]),
         "mc_ev_get_curve": (ctypes.c_int, [vp, i32, i32, P(i64), vp, vp, vp, vp]),
+        "mc_ev_state_info": (ctypes.c_int, [vp, P(i64), P(i64), P(i64)]),
+        "mc_ev_state_export": (ctypes.c_int, [vp, vp, i64, ctypes.c_int]),
+        "mc_ev_state_merge": (ctypes.c_int, [vp, vp, i64, ctypes.c_int]),
     }
     # MCGRAPH_LIB_PARTIAL=1 (A/B scripts only): an older variant library may lack newer entry points
     partial = os.environ.get("MCGRAPH_LIB_PARTIAL") == "1"
@@ -935,7 +938,44 @@ def _ev_methods():
                                                _ptr(fp), _ptr(fn)))
         return sc[:n.value], tp[:n.value], fp[:n.value], fn[:n.value]
 
-    for f in (ev_begin, ev_add_scan, ev_add_scan_clustered, ev_add_matches, ev_scan, ev_ap, ev_curve):
+    def ev_state_info(self):
+        """mc_ev_state_info: (runs, examples, bytes) of the accumulation's state buffer."""
+        r, e, b = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.L.mc_ev_state_info(self.h, ctypes.byref(r), ctypes.byref(e), ctypes.byref(b)))
+        return r.value, e.value, b.value
+
+    def ev_state(self, device: bool = False):
+        """mc_ev_state_export: the accumulation as its state buffer (include/mcgraph.h): a uint8 numpy array,
+        or with device a uint8 tensor on the context's device."""
+        n = self.ev_state_info()[2]
+        if device:
+            import torch
+            out = torch.empty(n, dtype=torch.uint8, device=self.torch_device)
+            self._check(self.L.mc_ev_state_export(self.h, ctypes.c_void_p(out.data_ptr()), n, 1))
+            return out
+        out = np.zeros(n, np.uint8)
+        self._check(self.L.mc_ev_state_export(self.h, _ptr(out), n, 0))
+        return out
+
+    def ev_merge_state(self, buf):
+        """mc_ev_state_merge: add a state buffer (bytes, a uint8 numpy array or a uint8 tensor; a tensor on the
+        context's device is read there) to the accumulation."""
+        if hasattr(buf, "data_ptr"):
+            import torch
+            if buf.dtype != torch.uint8 or not buf.is_contiguous():
+                raise ValueError("ev_merge_state: a tensor must be contiguous uint8")
+            if buf.device.type == "cuda":
+                torch.cuda.current_stream(buf.device).synchronize()   # the context reads it on its own stream
+                self._check(self.L.mc_ev_state_merge(self.h, ctypes.c_void_p(buf.data_ptr()), buf.numel(), 1))
+                return
+            buf = buf.numpy()
+        a = np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf)
+        if a.dtype != np.uint8 or a.ndim != 1:
+            raise ValueError("ev_merge_state: a uint8 vector")
+        self._check(self.L.mc_ev_state_merge(self.h, _ptr(a) if a.size else None, a.size, 0))
+
+    for f in (ev_begin, ev_add_scan, ev_add_scan_clustered, ev_add_matches, ev_scan, ev_ap, ev_curve, ev_state_info, ev_state,
+              ev_merge_state):
         setattr(Context, f.__name__, f)
 
 

@@ -7,6 +7,12 @@
 // (shared with mc_ev_add_matches) lays the tables out per class, uploads them and runs the greedy
 // pass, which appends (score, true) examples to per-(scan, class, overlap) regions whose sizes
 // are known beforehand.  All checks come before the first write to the accumulation.
+//
+// mc_ev_state_*: the accumulation as a state buffer (per cell the distinct scores with their true /
+// false counts, hard false negatives, flags).  ev_runs() builds it on the device from the same cell
+// segments the table is computed from and keeps it until the accumulation changes; ev_merge() checks
+// a buffer (header and per-cell sections on the host, the runs in a kernel) and appends its examples
+// as one unit per non-empty cell.
 
 namespace {
 
@@ -153,6 +159,7 @@ void ev_commit(mc_ctx *ctx, EvTables &&t)
     ev.last = std::move(t);
     ev.have_last = true;
     ev.ap_valid = false;
+    ev.runs_valid = false;
 }
 
 // the device half of mc_ev_add_scan*: every pointer is a device pointer
@@ -250,8 +257,8 @@ void ev_scan_device(mc_ctx *ctx, int64_t P, const int *gt, int K, const int64_t 
     ev_commit(ctx, std::move(t));
 }
 
-// the table over everything accumulated; curve_cell >= 0 also fills that cell's curve (device arrays)
-void ev_compute(mc_ctx *ctx, int curve_cell, double *cv_score, int64_t *cv_tp, int64_t *cv_fp, int64_t *cv_fn)
+// every unit's examples into its cell's segment of d_key / d_true (launches only); returns cell_off [NC + 1]
+int *ev_segments(mc_ctx *ctx)
 {
     EvState &ev = ctx->ev;
     hipStream_t s = ctx->stream;
@@ -259,25 +266,36 @@ void ev_compute(mc_ctx *ctx, int curve_cell, double *cv_score, int64_t *cv_tp, i
     const size_t n = static_cast<size_t>(ev.ex_used);
     ev.d_key.reserve(n * 8 + 8);
     ev.d_true.reserve(n + 8);
+    ev.d_cell.reserve((3 * static_cast<size_t>(NC) + 1) * 4);
+    int *cell_n = ev.d_cell.as<int>(), *cell_fill = cell_n + NC, *cell_off = cell_fill + NC;
+    MC_HIP(hipMemsetAsync(cell_n, 0, 2 * static_cast<size_t>(NC) * 4, s));
+    if (U)
+        hipLaunchKernelGGL(mc::k_ev_cell_count, grid_for(U), dim3(256), 0, s, U, ev.d_unit_cell.as<int>(),
+                           ev.d_unit_cnt.as<int>(), cell_n);
+    hipLaunchKernelGGL(mc::k_ev_cell_scan, dim3(1), dim3(1024), 0, s, NC, cell_n, cell_off);
+    if (U)
+        hipLaunchKernelGGL(mc::k_ev_gather, dim3(std::min(U, 8192)), dim3(256), 0, s, U, ev.d_unit_cell.as<int>(),
+                           ev.d_unit_cnt.as<int>(), ev.d_unit_off.as<int64_t>(), cell_off, cell_fill,
+                           ev.d_ex_key.as<unsigned long long>(), ev.d_ex_true.as<unsigned char>(),
+                           ev.d_key.as<unsigned long long>(), ev.d_true.as<unsigned char>());
+    return cell_off;
+}
+
+// the table over everything accumulated; curve_cell >= 0 also fills that cell's curve (device arrays)
+void ev_compute(mc_ctx *ctx, int curve_cell, double *cv_score, int64_t *cv_tp, int64_t *cv_fp, int64_t *cv_fn)
+{
+    EvState &ev = ctx->ev;
+    hipStream_t s = ctx->stream;
+    const int NC = ev.C * ev.O;
+    const size_t n = static_cast<size_t>(ev.ex_used);
     ev.d_prec.reserve((n + NC) * 8 + 8);
     ev.d_rec.reserve((n + NC) * 8 + 8);
-    ev.d_cell.reserve((3 * static_cast<size_t>(NC) + 1) * 4);
     ev.d_ap.reserve(static_cast<size_t>(NC) * 8);
     ev.d_stats.reserve(static_cast<size_t>(NC) * 32);
     ev.d_ndist.reserve(static_cast<size_t>(NC) * 4);
-    int *cell_n = ev.d_cell.as<int>(), *cell_fill = cell_n + NC, *cell_off = cell_fill + NC;
-    MC_HIP(hipMemsetAsync(cell_n, 0, 2 * static_cast<size_t>(NC) * 4, s));
     {
         TimedScope ts(ctx->timer, s, "ev_ap");
-        if (U)
-            hipLaunchKernelGGL(mc::k_ev_cell_count, grid_for(U), dim3(256), 0, s, U, ev.d_unit_cell.as<int>(),
-                               ev.d_unit_cnt.as<int>(), cell_n);
-        hipLaunchKernelGGL(mc::k_ev_cell_scan, dim3(1), dim3(1024), 0, s, NC, cell_n, cell_off);
-        if (U)
-            hipLaunchKernelGGL(mc::k_ev_gather, dim3(std::min(U, 8192)), dim3(256), 0, s, U, ev.d_unit_cell.as<int>(),
-                               ev.d_unit_cnt.as<int>(), ev.d_unit_off.as<int64_t>(), cell_off, cell_fill,
-                               ev.d_ex_key.as<unsigned long long>(), ev.d_ex_true.as<unsigned char>(),
-                               ev.d_key.as<unsigned long long>(), ev.d_true.as<unsigned char>());
+        const int *cell_off = ev_segments(ctx);
         hipLaunchKernelGGL(mc::k_ev_ap, dim3(std::min(NC, 8192)), dim3(256), 0, s, NC, cell_off,
                            ev.d_key.as<unsigned long long>(), ev.d_true.as<unsigned char>(),
                            ev.d_hardfn.as<unsigned long long>(), ev.d_flags.as<unsigned>(), ev.d_prec.as<double>(),
@@ -292,6 +310,180 @@ void ev_compute(mc_ctx *ctx, int curve_cell, double *cv_score, int64_t *cv_tp, i
     MC_HIP(hipStreamSynchronize(s));
     ctx->timer.collect();
     ev.ap_valid = true;
+}
+
+// ---- the accumulation as a state buffer (include/mcgraph.h, mc_ev_state_*) -----------------------
+constexpr int64_t kEvStateWord = (int64_t(1) << 32) | 0x5645434d;  // version 1, "MCEV"
+constexpr size_t kEvStateHeader = 48;
+
+struct EvLayout {  // byte offsets of the sections
+    size_t ids, ov, roff, hf, fl, key, nt, nf, bytes;
+};
+
+EvLayout ev_layout(int C, int O, int64_t R)
+{
+    auto up = [](size_t b) { return (b + 7) & ~size_t(7); };
+    const size_t NC = static_cast<size_t>(C) * O, r = static_cast<size_t>(R);
+    EvLayout L;
+    L.ids = kEvStateHeader;
+    L.ov = L.ids + up(4 * static_cast<size_t>(C));
+    L.roff = L.ov + 8 * static_cast<size_t>(O);
+    L.hf = L.roff + 8 * (NC + 1);
+    L.fl = L.hf + 8 * NC;
+    L.key = L.fl + up(4 * NC);
+    L.nt = L.key + 8 * r;
+    L.nf = L.nt + up(4 * r);
+    L.bytes = L.nf + up(4 * r);
+    return L;
+}
+
+// the state buffer of the accumulation in d_state, kept until the accumulation changes
+void ev_runs(mc_ctx *ctx)
+{
+    EvState &ev = ctx->ev;
+    if (ev.runs_valid) return;
+    hipStream_t s = ctx->stream;
+    const int C = ev.C, O = ev.O, NC = C * O;
+    ev.d_run.reserve((2 * static_cast<size_t>(NC) + 1) * 4);
+    int *cell_nrun = ev.d_run.as<int>(), *run_off = cell_nrun + NC;
+    int *cell_off;
+    {
+        TimedScope ts(ctx->timer, s, "ev_state");
+        cell_off = ev_segments(ctx);
+        hipLaunchKernelGGL(mc::k_ev_run_count, dim3(std::min(NC, 8192)), dim3(256), 0, s, NC, cell_off,
+                           ev.d_key.as<unsigned long long>(), ev.d_true.as<unsigned char>(), cell_nrun);
+        hipLaunchKernelGGL(mc::k_ev_cell_scan, dim3(1), dim3(1024), 0, s, NC, cell_nrun, run_off);
+        MC_HIP(hipGetLastError());
+    }
+    int tot[2] = {0, 0};  // runs, examples
+    MC_HIP(hipMemcpyAsync(&tot[0], run_off + NC, 4, hipMemcpyDeviceToHost, s));
+    MC_HIP(hipMemcpyAsync(&tot[1], cell_off + NC, 4, hipMemcpyDeviceToHost, s));
+    MC_HIP(hipStreamSynchronize(s));
+    const int64_t R = tot[0];
+    const EvLayout L = ev_layout(C, O, R);
+    std::vector<int64_t> head(L.roff / 8, 0);
+    head[0] = kEvStateWord, head[1] = C, head[2] = O, head[3] = ev.min_region, head[4] = ev.no_class ? 1 : 0, head[5] = R;
+    char *hb = reinterpret_cast<char *>(head.data());
+    std::memcpy(hb + L.ids, ev.class_ids.data(), static_cast<size_t>(C) * 4);
+    std::memcpy(hb + L.ov, ev.overlaps.data(), static_cast<size_t>(O) * 8);
+    ev.d_state.reserve(L.bytes);
+    char *D = ev.d_state.as<char>();
+    MC_HIP(hipMemsetAsync(D, 0, L.bytes, s));  // the padding of the 4-byte sections
+    MC_HIP(hipMemcpyAsync(D, hb, L.roff, hipMemcpyHostToDevice, s));
+    {
+        TimedScope ts(ctx->timer, s, "ev_state");
+        hipLaunchKernelGGL(mc::k_ev_run_write, dim3(std::min(NC, 8192)), dim3(256), 0, s, NC, cell_off,
+                           ev.d_key.as<unsigned long long>(), ev.d_true.as<unsigned char>(), run_off,
+                           ev.d_hardfn.as<unsigned long long>(), ev.d_flags.as<unsigned>(),
+                           reinterpret_cast<int64_t *>(D + L.roff), reinterpret_cast<int64_t *>(D + L.hf),
+                           reinterpret_cast<unsigned *>(D + L.fl), reinterpret_cast<unsigned long long *>(D + L.key),
+                           reinterpret_cast<unsigned *>(D + L.nt), reinterpret_cast<unsigned *>(D + L.nf));
+        MC_HIP(hipGetLastError());
+    }
+    MC_HIP(hipStreamSynchronize(s));  // the upload reads this call's host words
+    ctx->timer.collect();
+    ev.state_runs = R, ev.state_examples = tot[1], ev.state_bytes = static_cast<int64_t>(L.bytes);
+    ev.runs_valid = true;
+}
+
+void ev_merge(mc_ctx *ctx, const void *buf, int64_t bytes, bool on_device)
+{
+    EvState &ev = ctx->ev;
+    hipStream_t s = ctx->stream;
+    const int C = ev.C, O = ev.O, NC = C * O;
+    MC_REQUIRE(buf && bytes >= static_cast<int64_t>(kEvStateHeader), MC_ERR_INVALID, "state buffer is truncated");
+    MC_REQUIRE(!on_device || (reinterpret_cast<uintptr_t>(buf) & 7) == 0, MC_ERR_INVALID, "state buffer must be 8-byte aligned");
+    const char *src = static_cast<const char *>(buf);
+    auto take = [&](void *dst, size_t at, size_t n) {  // a part of the buffer to the host
+        if (on_device) fetch(ctx, dst, src + at, n);
+        else std::memcpy(dst, src + at, n);
+    };
+    int64_t hdr[6];
+    take(hdr, 0, kEvStateHeader);
+    MC_REQUIRE(hdr[0] == kEvStateWord, MC_ERR_INVALID, "not a state buffer of this version");
+    MC_REQUIRE(hdr[1] == C && hdr[2] == O && hdr[3] == ev.min_region && hdr[4] == (ev.no_class ? 1 : 0), MC_ERR_INVALID,
+               "state buffer of another configuration");
+    const int64_t R = hdr[5];
+    MC_REQUIRE(R >= 0 && R < (int64_t(1) << 31), MC_ERR_INVALID, "bad run count");
+    const EvLayout L = ev_layout(C, O, R);
+    MC_REQUIRE(static_cast<int64_t>(L.bytes) <= bytes, MC_ERR_INVALID, "state buffer is truncated");
+    // configuration and per-cell sections on the host
+    std::vector<int64_t> mid((L.key - L.ids) / 8);
+    take(mid.data(), L.ids, L.key - L.ids);
+    const char *mb = reinterpret_cast<const char *>(mid.data()) - L.ids;
+    MC_REQUIRE(std::memcmp(mb + L.ids, ev.class_ids.data(), static_cast<size_t>(C) * 4) == 0 &&
+                   std::memcmp(mb + L.ov, ev.overlaps.data(), static_cast<size_t>(O) * 8) == 0,
+               MC_ERR_INVALID, "state buffer of another configuration");
+    const int64_t *roff = reinterpret_cast<const int64_t *>(mb + L.roff), *hf = reinterpret_cast<const int64_t *>(mb + L.hf);
+    const uint32_t *fl = reinterpret_cast<const uint32_t *>(mb + L.fl);
+    MC_REQUIRE(roff[0] == 0 && roff[NC] == R, MC_ERR_INVALID, "run offsets must ascend from 0 to the run count");
+    std::vector<int> cells;
+    for (int c = 0; c < NC; c++) {
+        MC_REQUIRE(roff[c + 1] >= roff[c], MC_ERR_INVALID, "run offsets must ascend from 0 to the run count");
+        MC_REQUIRE(hf[c] >= 0, MC_ERR_INVALID, "negative hard false negative count");
+        MC_REQUIRE(fl[c] <= 3u, MC_ERR_INVALID, "unknown flag bits");
+        if (roff[c + 1] > roff[c]) cells.push_back(c);
+    }
+    const int U = static_cast<int>(cells.size());
+    const char *D = src;
+    if (!on_device) {
+        ev.d_merge.reserve(L.bytes);
+        MC_HIP(hipMemcpyAsync(ev.d_merge.ptr, src, L.bytes, hipMemcpyHostToDevice, s));
+        D = ev.d_merge.as<char>();
+    }
+    const int64_t *d_roff = reinterpret_cast<const int64_t *>(D + L.roff), *d_hf = reinterpret_cast<const int64_t *>(D + L.hf);
+    const unsigned *d_fl = reinterpret_cast<const unsigned *>(D + L.fl);
+    const unsigned long long *d_key = reinterpret_cast<const unsigned long long *>(D + L.key);
+    const unsigned *d_nt = reinterpret_cast<const unsigned *>(D + L.nt), *d_nf = reinterpret_cast<const unsigned *>(D + L.nf);
+    // the run checks behind one flag word, and the examples of all runs
+    ev.d_info.reserve(64);
+    MC_HIP(hipMemsetAsync(ev.d_info.ptr, 0, 16, s));
+    if (R) {
+        TimedScope ts(ctx->timer, s, "ev_merge");
+        hipLaunchKernelGGL(mc::k_ev_state_check, grid_for(R), dim3(256), 0, s, NC, R, d_roff, d_key, d_nt, d_nf,
+                           ev.d_info.as<int>(), reinterpret_cast<unsigned long long *>(ev.d_info.as<char>() + 8));
+        MC_HIP(hipGetLastError());
+    }
+    unsigned long long chk[2] = {0, 0};
+    fetch(ctx, chk, ev.d_info.ptr, 16);
+    const int bad = static_cast<int>(chk[0] & 0xffffffffu);
+    MC_REQUIRE(!(bad & 1), MC_ERR_INVALID, "a run without examples");
+    MC_REQUIRE(!(bad & 2), MC_ERR_INVALID, "a key that is no score (NaN)");
+    MC_REQUIRE(!(bad & 4), MC_ERR_INVALID, "keys must ascend strictly within a cell");
+    const unsigned long long total = chk[1];
+    MC_REQUIRE(total < (1ull << 31) && ev.ex_used + static_cast<int64_t>(total) < (int64_t(1) << 31) &&
+                   static_cast<int64_t>(ev.units) + U < (int64_t(1) << 31),
+               MC_ERR_UNSUPPORTED, "more than 2^31 examples");
+    // ---- from here on the accumulation changes ----
+    const int64_t add = static_cast<int64_t>(total);
+    ev_grow(ev.d_ex_key, ev.ex_used * 8, (ev.ex_used + add) * 8 + 8, s);
+    ev_grow(ev.d_ex_true, ev.ex_used, ev.ex_used + add + 8, s);
+    ev_grow(ev.d_unit_cell, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
+    ev_grow(ev.d_unit_cnt, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
+    ev_grow(ev.d_unit_off, static_cast<size_t>(ev.units) * 8, static_cast<size_t>(ev.units + U) * 8 + 8, s);
+    ev.d_tmp.reserve(static_cast<size_t>(U) * 4 + 8);
+    ev.d_words.reserve((static_cast<size_t>(R) + 1) * 4 + 8);
+    if (U) MC_HIP(hipMemcpyAsync(ev.d_tmp.ptr, cells.data(), static_cast<size_t>(U) * 4, hipMemcpyHostToDevice, s));
+    int *run_ex = ev.d_words.as<int>();
+    {
+        TimedScope ts(ctx->timer, s, "ev_merge");
+        if (R) {
+            hipLaunchKernelGGL(mc::k_ev_state_scan, dim3(1), dim3(1024), 0, s, static_cast<int>(R), d_nt, d_nf, run_ex);
+            hipLaunchKernelGGL(mc::k_ev_state_expand, grid_for(add), dim3(256), 0, s, static_cast<int>(R), run_ex, d_key, d_nt,
+                               ev.d_ex_key.as<unsigned long long>() + ev.ex_used, ev.d_ex_true.as<unsigned char>() + ev.ex_used);
+        }
+        hipLaunchKernelGGL(mc::k_ev_state_units, grid_for(std::max(NC, U)), dim3(256), 0, s, NC, U, ev.d_tmp.as<int>(), d_roff,
+                           run_ex, d_hf, d_fl, ev.ex_used, ev.d_unit_cell.as<int>() + ev.units, ev.d_unit_cnt.as<int>() + ev.units,
+                           ev.d_unit_off.as<int64_t>() + ev.units, ev.d_hardfn.as<unsigned long long>(),
+                           ev.d_flags.as<unsigned>());
+        MC_HIP(hipGetLastError());
+    }
+    MC_HIP(hipStreamSynchronize(s));  // the uploads read this call's host words
+    ctx->timer.collect();
+    ev.ex_used += add;
+    ev.units += U;
+    ev.ap_valid = false;
+    ev.runs_valid = false;
 }
 
 }  // namespace
@@ -334,7 +526,7 @@ int mc_ev_begin(mc_ctx *ctx, int32_t num_classes, const int32_t *class_ids, int3
         ev.min_region = min_region_size;
         ev.no_class = no_class != 0;
         ev.ex_used = 0, ev.units = 0;
-        ev.have_last = false, ev.ap_valid = false;
+        ev.have_last = false, ev.ap_valid = false, ev.runs_valid = false;
         ev.active = true;
     });
 }
@@ -475,6 +667,40 @@ int mc_ev_get_curve(mc_ctx *ctx, int32_t class_index, int32_t overlap_index, int
         };
         dn(scores, d_score), dn(tp, d_tp), dn(fp, d_fp), dn(fn, d_fn);
         MC_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int mc_ev_state_info(mc_ctx *ctx, int64_t *num_runs, int64_t *num_examples, int64_t *bytes)
+{
+    return guarded(ctx, [&] {
+        EvState &ev = ctx->ev;
+        MC_REQUIRE(ev.active, MC_ERR_STATE, "mc_ev_begin first");
+        ev_runs(ctx);
+        if (num_runs) *num_runs = ev.state_runs;
+        if (num_examples) *num_examples = ev.state_examples;
+        if (bytes) *bytes = ev.state_bytes;
+    });
+}
+
+int mc_ev_state_export(mc_ctx *ctx, void *buf, int64_t bytes, int on_device)
+{
+    return guarded(ctx, [&] {
+        EvState &ev = ctx->ev;
+        MC_REQUIRE(ev.active, MC_ERR_STATE, "mc_ev_begin first");
+        ev_runs(ctx);
+        MC_REQUIRE(buf && bytes >= ev.state_bytes, MC_ERR_INVALID, "buffer smaller than mc_ev_state_info reports");
+        hipStream_t s = ctx->stream;
+        MC_HIP(hipMemcpyAsync(buf, ev.d_state.ptr, static_cast<size_t>(ev.state_bytes),
+                              on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        MC_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int mc_ev_state_merge(mc_ctx *ctx, const void *buf, int64_t bytes, int on_device)
+{
+    return guarded(ctx, [&] {
+        MC_REQUIRE(ctx->ev.active, MC_ERR_STATE, "mc_ev_begin first");
+        ev_merge(ctx, buf, bytes, on_device != 0);
     });
 }
 

@@ -19,6 +19,12 @@
 //   k_ev_ap            workgroup per (class, overlap) cell: sort by score (LDS up to kEvSortCap
 //                      examples, in place in global memory above), one precision/recall point per
 //                      distinct score, step widths and the sum in index order
+//   k_ev_run_count / k_ev_run_write   the accumulation as runs (mc_ev_state_export): workgroup per
+//                      cell, the same sort (ev_block_sort), then per distinct key its true / false counts
+//   k_ev_state_check   mc_ev_state_merge: the checks of a buffer's runs behind one flag word, and
+//                      the 64-bit total of their examples
+//   k_ev_state_scan / k_ev_state_expand / k_ev_state_units   the runs back to examples, thread per
+//                      example, appended as one unit per non-empty cell
 // No FMA is written (the library is built with -ffp-contract=off).
 
 namespace mc {
@@ -512,6 +518,31 @@ __global__ __launch_bounds__(256) void k_ev_gather(int U, const int *__restrict_
     }
 }
 
+// Bitonic network with every exchange ascending, by the whole workgroup of 256 over K / T [0, n) in LDS
+// or global memory: positions >= n act as +inf and never move.  The order within equal keys is free.
+__device__ inline void ev_block_sort(unsigned long long *K, unsigned char *T, int n)
+{
+    const int tid = threadIdx.x;
+    auto cmpx = [&](int i, int l) {
+        if (l > i && l < n && K[l] < K[i]) {
+            const unsigned long long tk = K[i];
+            K[i] = K[l];
+            K[l] = tk;
+            const unsigned char tt = T[i];
+            T[i] = T[l];
+            T[l] = tt;
+        }
+    };
+    for (int64_t k = 2; (k >> 1) < n; k <<= 1) {
+        for (int i = tid; i < n; i += 256) cmpx(i, static_cast<int>(i ^ (k - 1)));
+        __syncthreads();
+        for (int64_t j = k >> 2; j > 0; j >>= 1) {
+            for (int i = tid; i < n; i += 256) cmpx(i, static_cast<int>(i ^ j));
+            __syncthreads();
+        }
+    }
+}
+
 // Workgroup per cell.  prec / rec: workspace of (examples + cells) doubles, cell c's at cell_off[c] + c.
 // curve_cell >= 0: that cell's distinct scores and (tp, fp, fn) go to cv_*.
 __global__ __launch_bounds__(256) void k_ev_ap(int NC, const int *__restrict__ cell_off, unsigned long long *__restrict__ key,
@@ -542,25 +573,7 @@ __global__ __launch_bounds__(256) void k_ev_ap(int NC, const int *__restrict__ c
             T = lt;
         }
         __syncthreads();
-        // bitonic network with every exchange ascending: positions >= n act as +inf and never move
-        auto cmpx = [&](int i, int l) {
-            if (l > i && l < n && K[l] < K[i]) {
-                const unsigned long long tk = K[i];
-                K[i] = K[l];
-                K[l] = tk;
-                const unsigned char tt = T[i];
-                T[i] = T[l];
-                T[l] = tt;
-            }
-        };
-        for (int64_t k = 2; (k >> 1) < n; k <<= 1) {
-            for (int i = tid; i < n; i += 256) cmpx(i, static_cast<int>(i ^ (k - 1)));
-            __syncthreads();
-            for (int64_t j = k >> 2; j > 0; j >>= 1) {
-                for (int i = tid; i < n; i += 256) cmpx(i, static_cast<int>(i ^ j));
-                __syncthreads();
-            }
-        }
+        ev_block_sort(K, T, n);
         int nt = 0;
         for (int i = tid; i < n; i += 256) nt += T[i];
         int ntrue;
@@ -612,6 +625,211 @@ __global__ __launch_bounds__(256) void k_ev_ap(int NC, const int *__restrict__ c
             stats[4 * c + 2] = hf;
             stats[4 * c + 3] = f;
             ndist[c] = nd;
+        }
+    }
+}
+
+// ---- the accumulation as runs (mc_ev_state_*) ---------------------------------------------------
+// A cell's examples as its distinct keys ascending, each with its count of true and false examples:
+// the form AP depends on (include/mcgraph.h, the state buffer).
+
+// Workgroup per cell, pass 1: the gathered segment sorted by key (left sorted in global memory) and
+// the number of its distinct keys.
+__global__ __launch_bounds__(256) void k_ev_run_count(int NC, const int *__restrict__ cell_off, unsigned long long *key,
+                                                      unsigned char *tru, int *__restrict__ cell_nrun)
+{
+    __shared__ unsigned long long lk[kEvSortCap];
+    __shared__ unsigned char lt[kEvSortCap];
+    __shared__ int wsum[17];
+    const int tid = threadIdx.x;
+    for (int c = blockIdx.x; c < NC; c += gridDim.x) {
+        const int b = cell_off[c], n = cell_off[c + 1] - b;
+        unsigned long long *K = key + b;
+        unsigned char *T = tru + b;
+        const bool lds = n <= kEvSortCap;
+        __syncthreads();
+        if (lds) {
+            for (int i = tid; i < n; i += 256) {
+                lk[i] = K[i];
+                lt[i] = T[i];
+            }
+            K = lk;
+            T = lt;
+        }
+        __syncthreads();
+        ev_block_sort(K, T, n);
+        int nd = 0;
+        for (int i = tid; i < n; i += 256) nd += (i == 0 || K[i] != K[i - 1]) ? 1 : 0;
+        int tot;
+        ev_block_scan(nd, wsum, tot);
+        if (tid == 0) cell_nrun[c] = tot;
+        if (lds)
+            for (int i = tid; i < n; i += 256) {
+                key[b + i] = lk[i];
+                tru[b + i] = lt[i];
+            }
+    }
+}
+
+// Workgroup per cell, pass 2, over the sorted segments: run j of the cell at run_off[c] + j.  The
+// first example of a run stores the counts of true / false examples below it; the differences of
+// neighbours are the run's own counts.
+__global__ __launch_bounds__(256) void k_ev_run_write(int NC, const int *__restrict__ cell_off,
+                                                      const unsigned long long *__restrict__ key,
+                                                      const unsigned char *__restrict__ tru, const int *__restrict__ run_off,
+                                                      const unsigned long long *__restrict__ hardfn,
+                                                      const unsigned *__restrict__ flags, int64_t *__restrict__ o_run_off,
+                                                      int64_t *__restrict__ o_hardfn, unsigned *__restrict__ o_flags,
+                                                      unsigned long long *__restrict__ o_key, unsigned *o_nt, unsigned *o_nf)
+{
+    __shared__ int wsum[17];
+    const int tid = threadIdx.x;
+    for (int c = blockIdx.x; c < NC; c += gridDim.x) {
+        const int b = cell_off[c], n = cell_off[c + 1] - b;
+        const int r0 = run_off[c], nr = run_off[c + 1] - r0;
+        const unsigned long long *K = key + b;
+        const unsigned char *T = tru + b;
+        if (tid == 0) {
+            o_run_off[c] = r0;
+            if (c == NC - 1) o_run_off[NC] = run_off[NC];
+            o_hardfn[c] = static_cast<int64_t>(hardfn[c]);
+            o_flags[c] = flags[c];
+        }
+        int below = 0, nd = 0;  // true examples / runs before the tile
+        for (int t0 = 0; t0 < n; t0 += 256) {
+            const int i = t0 + tid;
+            const bool in = i < n;
+            const int tv = in ? T[i] : 0;
+            const int first = in && (i == 0 || K[i] != K[i - 1]);
+            int tt, tf;
+            const int bt = ev_block_scan(tv, wsum, tt) + below;
+            const int j = ev_block_scan(first, wsum, tf) + nd;
+            if (first) {
+                o_key[r0 + j] = K[i];
+                o_nt[r0 + j] = static_cast<unsigned>(bt);
+                o_nf[r0 + j] = static_cast<unsigned>(i - bt);
+            }
+            below += tt;
+            nd += tf;
+        }
+        __syncthreads();  // the counts below every run are written
+        for (int j0 = 0; j0 < nr; j0 += 256) {
+            const int j = j0 + tid;
+            unsigned dt = 0, df = 0;
+            if (j < nr) {
+                const unsigned et = j + 1 < nr ? o_nt[r0 + j + 1] : static_cast<unsigned>(below);
+                const unsigned ef = j + 1 < nr ? o_nf[r0 + j + 1] : static_cast<unsigned>(n - below);
+                dt = et - o_nt[r0 + j];
+                df = ef - o_nf[r0 + j];
+            }
+            __syncthreads();  // entry j0 + 256 is read before the next tile overwrites it
+            if (j < nr) {
+                o_nt[r0 + j] = dt;
+                o_nf[r0 + j] = df;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// a key ev_key gives for a score that is no NaN: -inf .. +inf, without the key of -0.0
+__device__ __forceinline__ bool ev_key_ok(unsigned long long k)
+{
+    return k >= 0x000fffffffffffffull && k <= 0xfff0000000000000ull && k != 0x7fffffffffffffffull;
+}
+
+// The run checks of mc_ev_state_merge (run_off is checked by the host: from 0 ascending to R).
+// flag[0]: 1 a run without examples, 2 a key of no score, 4 keys not strictly ascending within a
+// cell; total: the examples of all runs.
+__global__ __launch_bounds__(256) void k_ev_state_check(int NC, int64_t R, const int64_t *__restrict__ run_off,
+                                                        const unsigned long long *__restrict__ key,
+                                                        const unsigned *__restrict__ nt, const unsigned *__restrict__ nf,
+                                                        int *__restrict__ flag, unsigned long long *__restrict__ total)
+{
+    int bad = 0;
+    unsigned long long sum = 0;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < R; i += static_cast<int64_t>(gridDim.x) * 256) {
+        const unsigned long long n = static_cast<unsigned long long>(nt[i]) + nf[i];
+        if (n == 0) bad |= 1;
+        sum += n;
+        const unsigned long long k = key[i];
+        if (!ev_key_ok(k)) bad |= 2;
+        int lo = 0, hi = NC;  // the cell of run i: the last c with run_off[c] <= i
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (run_off[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        if (i > run_off[lo] && !(key[i - 1] < k)) bad |= 4;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        bad |= __shfl_xor(bad, d, 64);
+        sum += __shfl_xor(sum, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) atomicOr(&flag[0], bad);
+        if (sum) atomicAdd(total, sum);
+    }
+}
+
+// one workgroup of 1024: run_ex[R + 1], the examples before every run (their total is below 2^31)
+__global__ __launch_bounds__(1024) void k_ev_state_scan(int R, const unsigned *__restrict__ nt, const unsigned *__restrict__ nf,
+                                                        int *__restrict__ run_ex)
+{
+    __shared__ int wsum[17];
+    const int ch = (R + 1023) / 1024;
+    const int lo = min(R, static_cast<int>(threadIdx.x) * ch), hi = min(R, lo + ch);
+    int n = 0;
+    for (int i = lo; i < hi; i++) n += static_cast<int>(nt[i] + nf[i]);
+    int tot;
+    int at = ev_block_scan(n, wsum, tot);
+    for (int i = lo; i < hi; i++) {
+        run_ex[i] = at;
+        at += static_cast<int>(nt[i] + nf[i]);
+    }
+    if (threadIdx.x == 0) run_ex[R] = tot;
+}
+
+// thread per example of the new region [0, run_ex[R]): its run by bisection, true for the run's first
+// n_true examples
+__global__ __launch_bounds__(256) void k_ev_state_expand(int R, const int *__restrict__ run_ex,
+                                                         const unsigned long long *__restrict__ key,
+                                                         const unsigned *__restrict__ nt, unsigned long long *__restrict__ ex_key,
+                                                         unsigned char *__restrict__ ex_true)
+{
+    const int64_t n = run_ex[R];
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; e < n; e += static_cast<int64_t>(gridDim.x) * 256) {
+        int lo = 0, hi = R;  // the last run with run_ex[r] <= e (runs are not empty)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (run_ex[mid] <= e) lo = mid;
+            else hi = mid;
+        }
+        ex_key[e] = key[lo];
+        ex_true[e] = (e - run_ex[lo] < static_cast<int64_t>(nt[lo])) ? 1 : 0;
+    }
+}
+
+// thread per cell: hard false negatives and flags added; thread per non-empty cell of the buffer
+// (cells[u], ascending): its examples as one unit
+__global__ __launch_bounds__(256) void k_ev_state_units(int NC, int U, const int *__restrict__ cells,
+                                                        const int64_t *__restrict__ run_off, const int *__restrict__ run_ex,
+                                                        const int64_t *__restrict__ hardfn, const unsigned *__restrict__ flags,
+                                                        int64_t ex_base, int *__restrict__ unit_cell, int *__restrict__ unit_cnt,
+                                                        int64_t *__restrict__ unit_off, unsigned long long *__restrict__ cell_hardfn,
+                                                        unsigned *__restrict__ cell_flags)
+{
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < max(NC, U); t += gridDim.x * 256) {
+        if (t < NC) {
+            cell_hardfn[t] += static_cast<unsigned long long>(hardfn[t]);
+            cell_flags[t] |= flags[t];
+        }
+        if (t < U) {
+            const int c = cells[t];
+            const int e0 = run_ex[run_off[c]], e1 = run_ex[run_off[c + 1]];
+            unit_cell[t] = c;
+            unit_cnt[t] = e1 - e0;
+            unit_off[t] = ex_base + e0;
         }
     }
 }

@@ -140,6 +140,10 @@ struct EvState {
     std::vector<int64_t> stats;
     std::vector<int32_t> ndist;
     DevBuf d_key, d_true, d_prec, d_rec, d_cell, d_ap, d_stats, d_ndist;
+    // the accumulation as runs (mc_ev_state_*): the state buffer of the last export, kept on the device
+    bool runs_valid = false;
+    int64_t state_runs = 0, state_examples = 0, state_bytes = 0;
+    DevBuf d_state, d_run, d_merge;
     // scratch of one mc_ev_add_scan / commit
     std::vector<int64_t> h_out;
     DevBuf d_info, d_in[5], d_cnt, d_inst, d_tmp_id, d_class, d_gcls, d_gid, d_gvert, d_pinst, d_pk, d_pair_gt, d_pair_int,

@@ -8,7 +8,10 @@ the masks as the graph input, ``mc_graph_build`` + ``mc_cluster_run``.
 
 With ``begin_evaluation`` and ``run_scene(..., post_process=..., gt_ids=...)`` every scene's final objects
 are also matched against its ground truth on the device (``mc_ev_add_scan_clustered``) and
-``evaluation()`` gives the reference's AP table over the sweep (evaluation/evaluate.py:53-224)."""
+``evaluation()`` gives the reference's AP table over the sweep (evaluation/evaluate.py:53-224).
+With N ranks every rank holds the examples of its own scenes: ``evaluation(group)`` gathers the ranks'
+accumulations as state buffers (``mc_ev_state_export``) onto one rank and merges them there
+(``mc_ev_state_merge``); ``save_evaluation`` / ``load_evaluation`` checkpoint the same buffer."""
 from __future__ import annotations
 
 import warnings
@@ -40,6 +43,40 @@ def compute_averages(ap, overlaps, class_labels) -> dict:
     return out
 
 
+def gather_states(state, group, dst: int = 0):
+    """The ranks' evaluation state buffers (``Context.ev_state``: uint8 numpy arrays, or uint8 tensors)
+    on group rank dst: a list with one uint8 tensor per rank there, None elsewhere.
+
+    Two collectives: an all-gather of the sizes, then a gather of uint8 tensors padded to the
+    largest size (an all-gather where the backend has no gather).  Host tensors under gloo, device
+    tensors under RCCL ("nccl"), decided as ``frame_shard.gather_masks`` does."""
+    import torch
+    import torch.distributed as dist
+    from .frame_shard import _comm_device, _gather_supported
+    t = state if hasattr(state, "data_ptr") else torch.from_numpy(np.ascontiguousarray(state, np.uint8))
+    world, me = dist.get_world_size(group), dist.get_rank(group)
+    dev = _comm_device(group, t.device)
+    n = t.numel()
+    sizes = torch.empty(world, dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(sizes, torch.tensor([n], dtype=torch.int64, device=dev), group=group)
+    sizes = [int(x) for x in sizes.cpu().tolist()]
+    nmax = max(sizes)                                   # a multiple of 8, as every state's size
+    buf = torch.zeros(nmax, dtype=torch.uint8, device=dev)
+    buf[:n] = t.to(dev)
+    if _gather_supported(group):
+        parts = [torch.empty(nmax, dtype=torch.uint8, device=dev) for _ in range(world)] if me == dst else None
+        dist.gather(buf, parts, dst=dist.get_global_rank(group, dst), group=group)
+        if me != dst:
+            return None
+    else:
+        allp = torch.empty(world * nmax, dtype=torch.uint8, device=dev)
+        dist.all_gather_into_tensor(allp, buf, group=group)
+        if me != dst:
+            return None
+        parts = list(allp.view(world, nmax))
+    return [parts[r][:sizes[r]] for r in range(world)]
+
+
 class SceneSweep:
     """One process's scenes on one device: ``run_scene`` per scene, the context reused across scenes
     (its S1 batches sized from the scenes before, within its HBM budget)."""
@@ -63,14 +100,60 @@ class SceneSweep:
         self._ev_labels = [str(c) for c in class_ids] if class_labels is None else list(class_labels)
         if len(self._ev_labels) != len(class_ids):
             raise ValueError("class_labels and class_ids differ in length")
+        self._ev_cfg = (np.asarray(class_ids, np.int32).copy(), self._ev_overlaps, int(min_region_size), bool(no_class))
 
-    def evaluation(self) -> dict:
-        """The AP table over the scenes evaluated so far: ``ap`` [C, O], ``stats`` [C, O, 4] and the
-        reference's averages (``compute_averages``: nanmean over the classes, the 0.25 overlap kept apart)."""
-        ap, stats = self.ctx.ev_ap()
+    def _table(self, ap, stats) -> dict:
         out = {"ap": ap, "stats": stats}
         out.update(compute_averages(ap, self._ev_overlaps, self._ev_labels))
         return out
+
+    def evaluation(self, group=None, dst: int = 0, broadcast: bool = False) -> dict | None:
+        """The AP table over the scenes evaluated so far: ``ap`` [C, O], ``stats`` [C, O, 4] and the
+        reference's averages (``compute_averages``: nanmean over the classes, the 0.25 overlap kept apart).
+
+        group (a torch.distributed process group, one rank per sweep process): the table over the
+        scenes of every rank.  Each rank exports its accumulation as a state buffer (``mc_ev_state_export``),
+        the buffers are gathered on group rank dst (``gather_states``), which merges them into a scratch
+        accumulation (``mc_ev_state_merge``) and returns its table; the other ranks return None, or
+        with broadcast the same dict.  The ranks' own accumulations are not changed and keep growing;
+        a rank without scenes contributes an empty state.  Collective: every rank of the group calls it."""
+        if group is None:
+            return self._table(*self.ctx.ev_ap())
+        import torch
+        import torch.distributed as dist
+        from . import _native
+        from .frame_shard import _comm_device
+        dev = _comm_device(group, self.ctx.torch_device)
+        me = dist.get_rank(group)
+        states = gather_states(self.ctx.ev_state(device=dev.type == "cuda"), group, dst)
+        C, O = len(self._ev_cfg[0]), len(self._ev_overlaps)
+        res = torch.empty(C * O * 5, dtype=torch.int64, device=dev)      # ap's bits, then stats
+        if me == dst:
+            if getattr(self, "_ev_scratch", None) is None:
+                self._ev_scratch = _native.Context(self.ctx.device_index)
+            self._ev_scratch.ev_begin(*self._ev_cfg)
+            for st in states:
+                self._ev_scratch.ev_merge_state(st)
+            ap, stats = self._ev_scratch.ev_ap()
+            if not broadcast:
+                return self._table(ap, stats)
+            res.copy_(torch.from_numpy(np.concatenate([ap.view(np.int64).ravel(), stats.ravel()])))
+        elif not broadcast:
+            return None
+        dist.broadcast(res, dist.get_global_rank(group, dst), group=group)
+        res = res.cpu().numpy()
+        return self._table(res[:C * O].view(np.float64).reshape(C, O).copy(), res[C * O:].reshape(C, O, 4).copy())
+
+    def save_evaluation(self, path) -> None:
+        """The accumulation so far to a file: its state buffer (include/mcgraph.h) and nothing else.
+        With ``load_evaluation`` the checkpoint of a long sweep."""
+        with open(path, "wb") as f:
+            f.write(self.ctx.ev_state().tobytes())
+
+    def load_evaluation(self, path) -> None:
+        """Merge a file written by ``save_evaluation`` into the current accumulation (after
+        ``begin_evaluation`` with the same configuration; anything else is an McError)."""
+        self.ctx.ev_merge_state(np.fromfile(path, np.uint8))
 
     def run_scene(self, points, depth, seg, intrinsics, poses, post_process=None, gt_ids=None) -> int:
         """points float32 [P,3], depth f32 [F,H,W], seg u8 [F,H,W], intrinsics f64 [F,4], poses f64
