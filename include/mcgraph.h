@@ -497,6 +497,50 @@ int mc_openvoc_query(mc_ctx *ctx, int32_t num_objects, const int64_t *obj_off, c
                      int32_t num_rows, int32_t dim, const float *features, int32_t num_labels,
                      const float *label_features, float temperature, int32_t *out_label);
 
+/* ---- CLIP crop preparation for representative masks ----------------------------------------------
+ * Replaces the input side of semantics/get_open-voc_features.py:44-99 (CroppedImageDataset.__getitem__
+ * with a Resize(bicubic) / ToTensor / Normalize preprocess): per mask (frame index, label) its
+ * bounding box in the segmentation frame, `levels` boxes at growing margins (mask2box_multi_level,
+ * :49-61), each crop rgb[top:bottom, left:right] pasted into a square of the pad colour (:75-82),
+ * resized to out_size x out_size as Pillow's 8-bit bicubic resize does (a square of that size
+ * passes through), and written channel-first as ((float32(v) / 255) - mean) / std.  Bit-exact; the
+ * model itself is the caller's.  DESIGN.md §2 (f5).
+ *
+ * Frames: seg uint8 [F, H, W] and rgb uint8 [F, H, W, 3] at one size, host arrays or, with
+ * on_device, device pointers (host frames: only the referenced ones are uploaded).  mask_frame /
+ * mask_label are host arrays (duplicates allowed, order kept) and are checked before anything is
+ * launched: a frame index outside [0, F) or a label outside [0, 255] is MC_ERR_INVALID, as are
+ * out_size outside [1, 4096], levels outside [1, 16] and a negative expansion.
+ *
+ * mc_crop_boxes: boxes [num_masks * levels * 4] = (left, top, right, bottom), right / bottom
+ * exclusive as the reference slices, and status [num_masks]: MC_CROP_OK, MC_CROP_ABSENT (no pixel
+ * of the label in its frame; the reference's np.min raises; boxes 0) or MC_CROP_EMPTY (a single
+ * pixel: every level's crop is 0 x 0).  Outputs are host arrays or, with out_on_device, device
+ * pointers; then the call does not wait for the stream.
+ * mc_crop_render: one chunk of masks into out, a device pointer to float32 [num_masks, levels, 3,
+ * out_size, out_size]; rows of a mask whose status is not MC_CROP_OK are zeros.  boxes / status as
+ * mc_crop_boxes wrote them, host arrays (checked: MC_ERR_INVALID for a box outside its frame) or,
+ * with boxes_on_device, device pointers (a box outside its frame renders as zeros).  Stream-ordered
+ * on the context stream; the call does not wait for it.  Scratch (per crop max(H, W) * out_size * 3
+ * bytes and its coefficient table) comes from the context and is bounded by
+ * mc_ctx_set_memory_budget (1 GiB when unset): a chunk is rendered in as many launches as that
+ * takes, MC_ERR_UNSUPPORTED when one mask alone exceeds it.
+ * mc_crop_coeffs: the device-computed table of one (in_size, out_size) in Pillow's layout, for
+ * diagnosis and tests: *ksize always; with bounds [out_size * 2] = (first tap, taps) and
+ * kk [out_size * ksize] (22-bit fixed point, unused taps 0) both non-NULL, the table. */
+#define MC_CROP_OK 0
+#define MC_CROP_ABSENT 1
+#define MC_CROP_EMPTY 2
+typedef struct { int32_t out_size, levels; double expansion; float mean[3], std[3]; uint8_t pad_rgb[3]; } mc_crop_params;
+void mc_crop_params_default(mc_crop_params *p);
+int mc_crop_boxes(mc_ctx *ctx, int32_t num_frames, int32_t H, int32_t W, const uint8_t *seg, int on_device,
+                  int32_t num_masks, const int32_t *mask_frame, const int32_t *mask_label,
+                  const mc_crop_params *params, int32_t *boxes, int32_t *status, int out_on_device);
+int mc_crop_render(mc_ctx *ctx, int32_t num_frames, int32_t H, int32_t W, const uint8_t *rgb, int on_device,
+                   int32_t num_masks, const int32_t *mask_frame, const int32_t *boxes, const int32_t *status,
+                   int boxes_on_device, const mc_crop_params *params, float *out);
+int mc_crop_coeffs(mc_ctx *ctx, int32_t in_size, int32_t out_size, int32_t *ksize, int32_t *bounds, int32_t *kk);
+
 /* host utility: packed little-endian bit rows (bit c of word c/64 = column c) -> one byte per
  * column, rows * ncols bytes (the dense bool point_frame_matrix the reference's callers read,
  * graph/construction.py:40,52), split over host threads.                                      */

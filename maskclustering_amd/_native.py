@@ -44,6 +44,7 @@ EXPORTED = [
     "mc_comm_unique_id", "mc_ctx_comm_init", "mc_ctx_attach_comm",
     "mc_ev_begin", "mc_ev_add_scan", "mc_ev_add_scan_clustered", "mc_ev_add_matches", "mc_ev_scan_info", "mc_ev_get_scan",
     "mc_ev_ap", "mc_ev_get_curve", "mc_ev_state_info", "mc_ev_state_export", "mc_ev_state_merge",
+    "mc_crop_params_default", "mc_crop_boxes", "mc_crop_render", "mc_crop_coeffs",
 ]
 MC_COMM_ID_BYTES = 128
 
@@ -105,6 +106,15 @@ class PPInfo(ctypes.Structure):
     _fields_ = [("num_objects", ctypes.c_int32), ("num_filtered", ctypes.c_int32), ("num_final", ctypes.c_int32),
                 ("num_entries", ctypes.c_int64), ("num_node_masks", ctypes.c_int64)]
 
+
+class CropParams(ctypes.Structure):
+    """mc_crop_params: output side, levels and expansion (get_open-voc_features.py:18,66), the Normalize
+    mean / std and the pad colour (:78)."""
+    _fields_ = [("out_size", ctypes.c_int32), ("levels", ctypes.c_int32), ("expansion", ctypes.c_double),
+                ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3), ("pad_rgb", ctypes.c_uint8 * 3)]
+
+
+MC_CROP_OK, MC_CROP_ABSENT, MC_CROP_EMPTY = 0, 1, 2
 
 _lib = None
 
@@ -209,6 +219,12 @@ def load():
         "mc_ev_state_info": (ctypes.c_int, [vp, P(i64), P(i64), P(i64)]),
         "mc_ev_state_export": (ctypes.c_int, [vp, vp, i64, ctypes.c_int]),
         "mc_ev_state_merge": (ctypes.c_int, [vp, vp, i64, ctypes.c_int]),
+        "mc_crop_params_default": (None, [P(CropParams)]),
+        "mc_crop_boxes": (ctypes.c_int, [vp, i32, i32, i32, vp, ctypes.c_int, i32, vp, vp, P(CropParams), vp, vp,
+                                         ctypes.c_int]),
+        "mc_crop_render": (ctypes.c_int, [vp, i32, i32, i32, vp, ctypes.c_int, i32, vp, vp, vp, ctypes.c_int,
+                                          P(CropParams), vp]),
+        "mc_crop_coeffs": (ctypes.c_int, [vp, i32, i32, P(i32), vp, vp]),
     }
     # MCGRAPH_LIB_PARTIAL=1 (A/B scripts only): an older variant library may lack newer entry points
     partial = os.environ.get("MCGRAPH_LIB_PARTIAL") == "1"
@@ -1015,6 +1031,134 @@ def _io_methods():
 
 
 _io_methods()
+
+
+def crop_params(**kw) -> CropParams:
+    """The reference's crop constants with open_clip's OpenAI mean / std, with optional overrides
+    (mean, std, pad_rgb as 3-sequences)."""
+    p = CropParams()
+    load().mc_crop_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        if k in ("mean", "std", "pad_rgb"):
+            v = type(getattr(p, k))(*v)
+        elif not hasattr(p, k):
+            raise TypeError(f"unknown crop parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _crop_methods():
+    def _frames(self, a, channels, name):
+        """(pointer, on_device, F, H, W, keep-alive) of a uint8 frame stack: numpy or a device tensor"""
+        nd = 4 if channels else 3
+        if hasattr(a, "data_ptr"):
+            import torch
+            if a.dtype != torch.uint8 or a.dim() != nd or not a.is_contiguous() or (channels and a.shape[3] != channels):
+                raise ValueError(f"{name}: a contiguous uint8 tensor [F, H, W{', 3' if channels else ''}]")
+            if a.device.type == "cuda":
+                return ctypes.c_void_p(a.data_ptr()), 1, a.shape[0], a.shape[1], a.shape[2], a
+            a = a.numpy()
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.uint8 or a.ndim != nd or (channels and a.shape[3] != channels):
+            raise ValueError(f"{name}: a uint8 array [F, H, W{', 3' if channels else ''}]")
+        return _ptr(a), 0, a.shape[0], a.shape[1], a.shape[2], a
+
+    def _order(self):
+        """Device tensors live on torch's current stream, the kernels run on the context's.  When the two
+        differ the host waits for torch's stream before the call and (True returned) for the context's
+        after it; when the context runs on torch's stream (set_stream) nothing waits."""
+        import torch
+        cur = torch.cuda.current_stream(self.torch_device)
+        if (cur.cuda_stream or 0) == (self.stream() or 0):
+            return False
+        cur.synchronize()
+        return True
+
+    def _i32(a):
+        """int32 vector of request indices; a value int32 cannot hold stays out of range"""
+        return np.ascontiguousarray(np.clip(np.asarray(a, np.int64).reshape(-1), -1, 2 ** 31 - 1), np.int32)
+
+    def crop_boxes(self, seg, mask_frame, mask_label, params: CropParams | None = None, device: bool = False):
+        """mc_crop_boxes: (boxes int32 [n, levels, 4] = left, top, right, bottom; status int32 [n]) of the
+        masks (mask_frame[i], mask_label[i]) in seg uint8 [F, H, W] (numpy, or a tensor on the context's
+        device).  device=True: tensors on the context's device (no host wait when the context runs on
+        torch's current stream); otherwise numpy arrays."""
+        prm = params or crop_params()
+        sp, sdev, F, H, W, _keep = _frames(self, seg, 0, "seg")
+        mf, ml = _i32(mask_frame), _i32(mask_label)
+        if len(mf) != len(ml):
+            raise ValueError("mask_frame and mask_label differ in length")
+        n, L = len(mf), int(prm.levels)
+        if device:
+            import torch
+            boxes = torch.zeros((n, max(L, 0), 4), dtype=torch.int32, device=self.torch_device)
+            status = torch.zeros(n, dtype=torch.int32, device=self.torch_device)
+            settle = _order(self)
+            bp, stp = ctypes.c_void_p(boxes.data_ptr()), ctypes.c_void_p(status.data_ptr())
+        else:
+            boxes, status = np.zeros((n, max(L, 0), 4), np.int32), np.zeros(n, np.int32)
+            bp, stp = _ptr(boxes), _ptr(status)
+            settle = False   # host outputs: the call waits itself
+            if sdev:
+                _order(self)
+        self._check(self.L.mc_crop_boxes(self.h, F, H, W, sp, sdev, n, _ptr(mf), _ptr(ml), ctypes.byref(prm), bp, stp,
+                                         1 if device else 0))
+        if settle:
+            self.synchronize()
+        return boxes, status
+
+    def crop_render(self, rgb, mask_frame, boxes, status, params: CropParams | None = None, out=None):
+        """mc_crop_render: float32 [n, levels, 3, S, S] on the context's device for one chunk of masks.
+        rgb uint8 [F, H, W, 3] (numpy or device tensor); boxes / status as crop_boxes returned them
+        (numpy, or device tensors).  With the context on torch's current stream (set_stream) the call
+        is stream-ordered and nothing waits; otherwise the host waits for the context's stream."""
+        import torch
+        prm = params or crop_params()
+        rp, rdev, F, H, W, _keep = _frames(self, rgb, 3, "rgb")
+        mf = _i32(mask_frame)
+        n, L, S = len(mf), int(prm.levels), int(prm.out_size)
+        on_dev = hasattr(boxes, "data_ptr")
+        if on_dev != hasattr(status, "data_ptr"):
+            raise ValueError("boxes and status must both be numpy arrays or both device tensors")
+        if on_dev:
+            if boxes.dtype != torch.int32 or status.dtype != torch.int32 or boxes.device.type != "cuda" or \
+                    status.device.type != "cuda" or not boxes.is_contiguous() or not status.is_contiguous():
+                raise ValueError("boxes / status: contiguous int32 device tensors")
+            if boxes.numel() != n * L * 4 or status.numel() != n:
+                raise ValueError("boxes / status do not match the masks")
+            bp, stp = ctypes.c_void_p(boxes.data_ptr()), ctypes.c_void_p(status.data_ptr())
+        else:
+            boxes = np.ascontiguousarray(boxes, np.int32)
+            status = np.ascontiguousarray(status, np.int32)
+            if boxes.size != n * L * 4 or status.size != n:
+                raise ValueError("boxes / status do not match the masks")
+            bp, stp = _ptr(boxes), _ptr(status)
+        if out is None:
+            out = torch.empty((n, max(L, 0), 3, max(S, 0), max(S, 0)), dtype=torch.float32, device=self.torch_device)
+        elif out.dtype != torch.float32 or out.device.type != "cuda" or not out.is_contiguous() or \
+                out.numel() != n * L * 3 * S * S:
+            raise ValueError("out: a contiguous float32 device tensor [n, levels, 3, S, S]")
+        settle = _order(self)
+        self._check(self.L.mc_crop_render(self.h, F, H, W, rp, rdev, n, _ptr(mf), bp, stp, 1 if on_dev else 0,
+                                          ctypes.byref(prm), ctypes.c_void_p(out.data_ptr())))
+        if settle:
+            self.synchronize()
+        return out
+
+    def crop_coeffs(self, in_size, out_size):
+        """mc_crop_coeffs: (ksize, bounds int32 [out_size, 2], kk int32 [out_size, ksize]) computed on the device."""
+        k = ctypes.c_int32(0)
+        self._check(self.L.mc_crop_coeffs(self.h, int(in_size), int(out_size), ctypes.byref(k), None, None))
+        bounds = np.zeros((int(out_size), 2), np.int32)
+        kk = np.zeros((int(out_size), k.value), np.int32)
+        self._check(self.L.mc_crop_coeffs(self.h, int(in_size), int(out_size), ctypes.byref(k), _ptr(bounds), _ptr(kk)))
+        return k.value, bounds, kk
+
+    for f in (crop_boxes, crop_render, crop_coeffs):
+        setattr(Context, f.__name__, f)
+
+
+_crop_methods()
 
 
 def bits_unpack(words, ncols):

@@ -18,6 +18,7 @@
 #include "mc_bp_plan.hpp"
 #include "mc_graph_plan.hpp"
 #include "mc_pp_plan.hpp"
+#include "mc_crop_plan.hpp"
 #include "mc_kernels.inl"
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
@@ -26,6 +27,7 @@
 #include "mc_io_kernels.inl"
 #include "mc_shard_kernels.inl"
 #include "mc_ov_kernels.inl"
+#include "mc_crop_kernels.inl"
 #include "mc_setorder.inl"
 
 using mc::DevBuf;
@@ -150,6 +152,15 @@ struct EvState {
         d_out, d_words, d_tmp;
 };
 
+// CLIP crop preparation (mc_crop_*; the host code is mc_crop_host.inl): the context's pools
+struct CropState {
+    DevBuf tab, frames, slot, label;          // boxes: per-frame label tables, the referenced frames, per-mask slot / label
+    DevBuf in_seg, in_rgb, in_boxes, in_status, out_boxes, out_status;  // host arguments' device copies
+    DevBuf mframe, lut, bounds, kk, tmp;      // render: per-mask frame, 3 x 256 table, coefficient tables, intermediate
+    std::vector<int32_t> h_frames, h_slot, h_label, h_mframe;  // staged until the next call
+    std::vector<float> h_lut;
+};
+
 }  // namespace
 
 struct mc_ctx {
@@ -240,6 +251,7 @@ struct mc_ctx {
     DevBuf d_pp_fslot, d_pp_finobj, d_pp_finnode, d_pp_opoff, d_pp_omoff, d_pp_opts, d_pp_omask, d_pp_ocov, d_pp_repre;
 
     EvState ev;  // AP evaluation (mc_ev_*)
+    CropState crop;  // CLIP crop preparation (mc_crop_*)
 };
 
 namespace {
@@ -458,6 +470,7 @@ int mc_debug_counters(mc_ctx *ctx, int64_t *out, int32_t n, int reset)
 #include "mc_shard_host.inl"
 #include "mc_bp_host.inl"
 #include "mc_pp_host.inl"
+#include "mc_crop_host.inl"
 
 extern "C" {
 

@@ -7,7 +7,8 @@ reference's ``main.py`` / ``run.py`` run unchanged on the device path:
     utils.mask_backprojection   -> maskclustering_amd.utils.mask_backprojection
     utils.post_process          -> maskclustering_amd.utils.post_process
     semantics.open-voc_query    -> maskclustering_amd/semantics/open_voc_query.py
-                                   (run.py:102 runs it with ``python -m``: a meta-path finder)
+    semantics.get_open-voc_features -> maskclustering_amd/semantics/get_open_voc_features.py
+                                   (run.py runs both with ``python -m``: a meta-path finder)
 
 Every other reference module (utils.config, dataset.*, ...)
 is imported from the reference as usual.  ``integration/sitecustomize.py`` calls
@@ -31,6 +32,7 @@ ALIASES = {
 # sys.modules alias
 SCRIPTS = {
     "semantics.open-voc_query": "maskclustering_amd.semantics.open_voc_query",
+    "semantics.get_open-voc_features": "maskclustering_amd.semantics.get_open_voc_features",
 }
 
 
