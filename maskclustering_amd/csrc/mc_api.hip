@@ -90,6 +90,7 @@ struct BpState {
     DevBuf bm, tmp, kflag, ksize, midx, moff, out_col, out_label, out_off;
     DevBuf cls_list, nbl, lean, vox_order;  // denoise size-class slot lists; per-workgroup eps-neighbour lists, lean scratch
     DevBuf vx_pvid, vx_list, vx_fb;  // voxel_down_sample: per-pixel voxel ids and voxel lists of k_bp_voxel_lds; its overflow slots
+    DevBuf q_fb;       // ball query: the slots k_bp_query_lds hands to k_bp_query
     DevBuf scanm;      // block sums of the multi-workgroup scans
     DevBuf slot_grid;  // denoise: grid origin / extent of the slots with points queued for the k-NN ring search
     DevBuf pack;       // the batch's readback, packed (k_bp_pack)

@@ -41,6 +41,7 @@ enum BpStat : int {
     BS_DQ,                                // points queued for the k-NN ring search
     BS_DNERR,                             // denoise internal-error bits (queue entry / region out of range)
     BS_PXOVF,                             // the batch's mask pixels exceed the capacity: grown, batch redone
+    BS_QFB,                               // slots the staged ball query hands to k_bp_query
     BS_COUNT
 };
 
@@ -87,6 +88,9 @@ inline size_t lean_offset(const mc_ctx *ctx, int cls) { return bp_class_offset(c
 // query 8.4 -> 6.5 ms per scene; 32 entries: 89 VGPRs, five).  One point bitmap per workgroup.
 constexpr int kBpQueryWgPerCu20 = 6, kBpQueryWgPerCu32 = 5;
 constexpr int kBpQueryWgPerCuMax = std::max(kBpQueryWgPerCu20, kBpQueryWgPerCu32);
+// workgroups per CU of k_bp_query_lds: its 30.8 KB of LDS (the crop, the cell table, the staging list /
+// accepted ids and flags) fit five times into a CU's 160 KB
+constexpr int kBpQueryLdsWgPerCu = 5;
 
 // Test and tuning knobs of S1, read at the start of every call (tests change them between calls on
 // one context)
@@ -102,6 +106,13 @@ struct BpKnobs {
     int nbcap = mc::kBpNbCap;  // MC_BP_NBCAP: eps lists read only up to this many entries (the rest take the cell walks)
     int tail_wg = 8;           // MC_BP_TAILWG: workgroups per CU of k_bp_denoise_tail
     int stage_threads = 1;     // MC_STAGE_THREADS: host threads filling the pinned staging chunks
+    // the staged ball query (k_bp_query_lds): MC_BP_QUERY_STAGED=0 hands every slot to k_bp_query;
+    // MC_BP_QUERY_CELLS / MC_BP_QUERY_CAND: a slot with more box cells / cropped scene points goes to
+    // k_bp_query (at most the compiled LDS sizes); MC_BP_QUERY_GRID: its workgroups in all (0 = by CU
+    // count; 1 makes one workgroup take every slot in turn)
+    bool q_staged = true;
+    int q_cells = mc::kBpQcCells, q_cand = mc::kBpQcCand, q_grid = 0;
+    bool q_report = false;     // MC_BP_QUERY_REPORT=1: per batch, the slots and how many took k_bp_query (stderr)
 };
 
 BpKnobs bp_read_knobs(mc_ctx *ctx)
@@ -123,6 +134,11 @@ BpKnobs bp_read_knobs(mc_ctx *ctx)
     }
     if (const char *e = getenv("MC_BP_NBCAP")) k.nbcap = std::min(mc::kBpNbCap, std::max(1, atoi(e)));
     if (const char *e = getenv("MC_BP_TAILWG")) k.tail_wg = std::max(1, atoi(e));
+    if (const char *e = getenv("MC_BP_QUERY_STAGED")) k.q_staged = atoi(e) != 0;
+    if (const char *e = getenv("MC_BP_QUERY_CELLS")) k.q_cells = std::min(mc::kBpQcCells, std::max(1, atoi(e)));
+    if (const char *e = getenv("MC_BP_QUERY_CAND")) k.q_cand = std::min(mc::kBpQcCand, std::max(0, atoi(e)));
+    if (const char *e = getenv("MC_BP_QUERY_GRID")) k.q_grid = std::max(1, atoi(e));
+    if (const char *e = getenv("MC_BP_QUERY_REPORT")) k.q_report = atoi(e) != 0;
     k.stage_threads = stage_threads_knob(static_cast<int>(std::min(8u, std::max(1u, std::thread::hardware_concurrency()))));
     return k;
 }
@@ -140,7 +156,8 @@ void bp_reserve(mc_ctx *ctx, int fb, int H, int W, int nbands, size_t mask_px, h
     bp.fflags.reserve(static_cast<size_t>(fb) * 4);
     bp.stat.reserve(BS_COUNT * 4);
     for (DevBuf *b : {&bp.cand, &bp.npix, &bp.slot_of, &bp.slot_frame, &bp.slot_id, &bp.slot_np, &bp.slot_pix, &bp.slot_nv,
-                      &bp.slot_m, &bp.slot_ns, &bp.slot_nn, &bp.slot_toff, &bp.slot_cov, &bp.kflag, &bp.ksize, &bp.vox_order})
+                      &bp.slot_m, &bp.slot_ns, &bp.slot_nn, &bp.slot_toff, &bp.slot_cov, &bp.kflag, &bp.ksize, &bp.vox_order,
+                      &bp.q_fb})
         b->reserve(slots * 4);
     for (DevBuf *b : {&bp.csidx, &bp.poff, &bp.midx, &bp.moff}) b->reserve((slots + 1) * 4);
     bp.slot_box.reserve(slots * 6 * 4);
@@ -523,27 +540,36 @@ void bp_launch_denoise(mc_ctx *ctx, hipStream_t s, const BpBatch &bt, const BpKn
 
 // scene points within the ball radius of each slot's points (PW: words of a point bitmap; tmp_cap:
 // ints of the neighbour-set pool), then the kept masks' indices and offsets
-void bp_launch_query(mc_ctx *ctx, hipStream_t s, const BpBatch &bt, int PW, size_t tmp_cap)
+void bp_launch_query(mc_ctx *ctx, hipStream_t s, const BpBatch &bt, int PW, size_t tmp_cap, const BpKnobs &kn)
 {
     BpState &bp = ctx->bp;
     int *st = bt.st;
     TimedScope ts(ctx->timer, s, "bp_query");
+    const int tcap = static_cast<int>(std::min<size_t>(tmp_cap, INT_MAX));
+    // the slots whose box cells and cropped scene points fit LDS (largest first); the rest go to q_fb
+    hipLaunchKernelGGL(mc::k_bp_query_lds, dim3(kn.q_grid ? kn.q_grid : ctx->num_cu * kBpQueryLdsWgPerCu), dim3(256), 0, s,
+                       st + BS_NS, bp.slot_pix.as<int>(), bp.slot_ns.as<int>(), bp.slot_box.as<float>(),
+                       bp.qpts.as<float>(), bt.dv, bp.gpts.as<float4>(), bp.gcell.as<unsigned long long>(),
+                       bp.gstart.as<int>(), bp.gnb, bp.tmp.as<int>(), tcap, st + BS_TOP, bp.slot_nn.as<int>(),
+                       bp.slot_toff.as<int>(), bp.slot_cov.as<int>(), st + BS_OVF, bp.vox_order.as<int>(),
+                       bp.kflag.as<int>(), bp.ksize.as<int>(), bp.q_fb.as<int>(), st + BS_QFB,
+                       kn.q_staged ? kn.q_cells : 0, kn.q_cand);
+    bp_debug_sync(s, "k_bp_query_lds");
+    // k_bp_query over that list (few slots, the large ones: workgroups beyond its length end at once)
     auto query = [&](auto kern, int wg_per_cu) {
         const int grid = ctx->num_cu * wg_per_cu;
         MC_REQUIRE(static_cast<size_t>(grid) * PW * 8 <= bp.bm.bytes, MC_ERR_HIP,
                    "query grid beyond its point bitmaps (internal error)");
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, st + BS_NS, bp.slot_pix.as<int>(), bp.slot_ns.as<int>(),
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, st + BS_QFB, bp.slot_pix.as<int>(), bp.slot_ns.as<int>(),
                            bp.slot_box.as<float>(), bp.qpts.as<float>(), bt.dv, bp.gpts.as<float4>(), bp.gidx.as<int>(),
                            bp.gcell.as<unsigned long long>(), bp.gstart.as<int>(), bp.gnb,
-                           bp.bm.as<unsigned long long>(), PW, bp.tmp.as<int>(),
-                           static_cast<int>(std::min<size_t>(tmp_cap, INT_MAX)), st + BS_TOP, bp.slot_nn.as<int>(),
-                           bp.slot_toff.as<int>(), bp.slot_cov.as<int>(), st + BS_OVF, bp.vox_order.as<int>());
+                           bp.bm.as<unsigned long long>(), PW, bp.tmp.as<int>(), tcap, st + BS_TOP, bp.slot_nn.as<int>(),
+                           bp.slot_toff.as<int>(), bp.slot_cov.as<int>(), st + BS_OVF, bp.q_fb.as<int>(),
+                           bp.kflag.as<int>(), bp.ksize.as<int>());
     };
     if (bt.dv.kball <= 20) query(mc::k_bp_query<1, 20>, kBpQueryWgPerCu20);
     else query(mc::k_bp_query<1, mc::kBpBallMax>, kBpQueryWgPerCu32);
     bp_debug_sync(s, "k_bp_query");
-    hipLaunchKernelGGL(mc::k_bp_keepflags, grid_for(bt.nslot), dim3(256), 0, s, st + BS_NS, bp.slot_nn.as<int>(),
-                       bp.kflag.as<int>(), bp.ksize.as<int>());
     mc::scan_device_multi(s, st + BS_NS, bt.nslot, bp.scanm.as<int>(), bp.kflag.as<int>(), bp.midx.as<int>(), st + BS_M,
                           bp.ksize.as<int>(), bp.moff.as<int>(), st + BS_NNZ);
     bp_debug_sync(s, "bp_query");
@@ -723,13 +749,15 @@ void bp_run(mc_ctx *ctx, int F, int H, int W, BpFrames src, const mc_bp_params *
         bp_launch_pixels(ctx, s, bt);
         bp_launch_voxel(ctx, s, bt, kn.vx_global);
         bp_launch_denoise(ctx, s, bt, kn);
-        bp_launch_query(ctx, s, bt, PW, tmp_cap);
+        bp_launch_query(ctx, s, bt, PW, tmp_cap, kn);
         MC_HIP(hipMemcpyAsync(hs, st, BS_COUNT * 4, hipMemcpyDeviceToHost, s));
         bp_stage_to(ctx, src, std::min(F, b0 + fb + FB), H, W, kn.stage_threads);  // the host copies the next batch while this one computes
         pend.append(bp, prm.few_points);                                           // and appends the previous batch's results
         MC_HIP(hipStreamSynchronize(s));
         ctx->timer.collect();
         const BpVerdict v = bp_check_batch(ctx, hs, b0);
+        if (kn.q_report)
+            fprintf(stderr, "[mc bp] batch at frame %d: %d slots, %d took k_bp_query\n", b0, hs[BS_NS], hs[BS_QFB]);
         const double frac = static_cast<double>(hs[BS_NPX]) / (static_cast<double>(fb) * HW);
         if (v == BpVerdict::kRedoPixels) {  // grow to the share the batch showed, or take fewer frames, and redo it
             bp.mfrac = std::max(bp.mfrac, frac);

@@ -9,7 +9,7 @@ import sys
 GROUPS = [("pixels", ("k_bp_count", "k_bp_frames", "k_bp_slots", "k_bp_compact")),
           ("voxel", ("k_bp_vox_order", "k_bp_voxel")),
           ("denoise", ("k_bp_classify", "k_bp_denoise")),
-          ("query", ("k_bp_query", "k_bp_keepflags", "k_bp_emit"))]
+          ("query", ("k_bp_query", "k_bp_emit"))]
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if "mc::" in r["Kernel_Name"]]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 last = int(sys.argv[2]) if len(sys.argv) > 2 else 8

@@ -59,6 +59,12 @@ print("k_bp_voxel_lds workgroup-busy shares:", {n: f"{100 * v / vtot:.1f} %" for
       zip(("0 min bound", "1a points+keys+probes", "1b masks+ids+sums", "1 exit", "2 means + slot set-up"), vt)},
       "total ms", round(vtot / 1e5, 2))
 st = ctx.bp_candidates()
+# the two ball-query kernels (set MC_BP_QUERY_STAGED=0 for k_bp_query on every slot)
+nq = max(int((st[:, 5] >= 25).sum()), 1)
+qv = [float(buf[k]) / 100.0 for k in range(41, 48)]
+print("query slots", nq, "k_bp_query us/slot: walk", round(qv[1] / nq, 2), "scan+emit", round(qv[2] / nq, 2),
+      "| k_bp_query_lds us/slot: find", round(qv[3] / nq, 2), "scan+place", round(qv[4] / nq, 2), "walk",
+      round(qv[5] / nq, 2), "emit", round(qv[6] / nq, 2))
 for c, n in ((2, "npix"), (3, "nvox"), (4, "ndbscan"), (5, "nsor")):
     v = st[:, c]
     print(n, "mean", round(float(v.mean()), 1), "p99", int(np.percentile(v, 99)), "max", int(v.max()))

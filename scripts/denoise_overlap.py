@@ -31,7 +31,7 @@ for i0 in starts[-last:]:
              "voxel" if ("k_bp_voxel" in n or ("k_bp_vox_order" in n and not grp["voxel"])) else
              "denoise" if ("k_bp_denoise" in n or "k_bp_classify" in n or
                            ("k_bp_vox_order" in n and grp["voxel"])) else
-             "query" if any(p in n for p in ("k_bp_query", "k_bp_keepflags", "k_bp_emit")) else None)
+             "query" if any(p in n for p in ("k_bp_query", "k_bp_emit")) else None)
         if g:
             grp[g].append(r)
     line = []

@@ -36,7 +36,8 @@ GROUPS = {
     "bp_voxel": (["mc::k_bp_voxel", "mc::k_bp_vox_order"], ["mc::k_bp_voxel_lds<256"]),
     "bp_denoise": (["mc::k_bp_denoise", "mc::k_bp_classify", "mc::k_bp_knn_ring", "mc::k_bp_vox_order"],
                    ["mc::k_bp_classify"]),
-    "bp_query": (["mc::k_bp_query", "mc::k_bp_keepflags", "mc::k_bp_emit"], ["mc::k_bp_query", "mc::k_bp_emit"]),
+    # (the prefix k_bp_query covers k_bp_query_lds and the k_bp_query it hands slots to)
+    "bp_query": (["mc::k_bp_query", "mc::k_bp_emit"], ["mc::k_bp_query_lds", "mc::k_bp_emit"]),
 }
 
 
