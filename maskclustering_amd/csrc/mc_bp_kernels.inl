@@ -22,6 +22,7 @@
 // count), so no allocation depends on a device result.
 #include "mc_internal.hpp"
 #include "mc_bp_qcell.hpp"
+#include "mc_bp_world.hpp"
 
 #include <cfloat>
 
@@ -88,29 +89,14 @@ __device__ __forceinline__ unsigned long long pack3(int x, int y, int z)
 }
 // scene_cell (the 2r scene grid's cell coordinate) and kCellBias: mc_bp_qcell.hpp
 
-// a / b rounded to nearest, from rb = RN(1 / b) computed once per divisor (Markstein: q0 = RN(a rb),
-// r = a - b q0 is exact by FMA, and RN(q0 + r rb) is the correctly rounded quotient for normal operands
-// whose quotient neither overflows nor underflows): a multiply and two FMAs instead of the
-// division sequence (v_rcp_f64, scale, five FMAs, fixup), the same bits as a / b
-// (tests/test_div_rn_cpu.py checks the identity on operands of the ranges here).  S1's per-pixel
-// divisions are these: the unprojection by fx and fy, and the voxel index by the voxel size.
-__device__ __forceinline__ double div_rn(double a, double b, double rb)
-{
-    const double q0 = a * rb;
-    const double r = fma(-b, q0, a);
-    return fma(r, rb, q0);
-}
+// div_rn (a / b from RN(1 / b): a multiply and two FMAs instead of the division sequence v_rcp_f64, scale,
+// five FMAs, fixup; the same bits as a / b), bp_recip, and the world point of a pixel in its general and
+// affine forms (bp_world, bp_world_affine, bp_pose_affine): mc_bp_world.hpp.  S1's per-pixel divisions
+// are div_rn's: the unprojection by fx and fy, and the voxel index by the voxel size.
 
 // (a1, u1): Open3D create_from_depth_image + transform, in double, no FMA
 // floor(a / b) of the cell indices (the denoise's grid; per voxel, not per pixel)
 __device__ __forceinline__ double floor_div(double a, double b) { return floor(a / b); }
-
-// the per-frame reciprocals of bp_world's divisors: rk[0] = RN(1 / fx), rk[1] = RN(1 / fy)
-__device__ __forceinline__ void bp_recip(const double *__restrict__ K, double rk[2])
-{
-    rk[0] = 1.0 / K[0];
-    rk[1] = 1.0 / K[1];
-}
 
 // a value equal in every lane, moved to scalar registers (frees its VGPRs for the rest of the slot)
 __device__ __forceinline__ double uniform_d(double v)
@@ -120,20 +106,41 @@ __device__ __forceinline__ double uniform_d(double v)
     const int hi = __builtin_amdgcn_readfirstlane(static_cast<int>(b >> 32));
     return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo));
 }
-__device__ __forceinline__ void bp_world(const double *__restrict__ K, const double *__restrict__ T, int u, int v,
-                                         float d, double &ox, double &oy, double &oz, const double *rk)
+// the slot's choice between bp_world and bp_world_affine, made once from the frame's K and pose (scalar
+// loads: the same in every lane) and held in a scalar register, so that the branches on it are uniform
+__device__ __forceinline__ bool bp_slot_affine(const double *__restrict__ K, const double *__restrict__ T, double trunc)
 {
-    const double z = static_cast<double>(d);
-    const double x = div_rn((static_cast<double>(u) - K[2]) * z, K[0], rk[0]);
-    const double y = div_rn((static_cast<double>(v) - K[3]) * z, K[1], rk[1]);
-    double r[4];
+    return __builtin_amdgcn_readfirstlane(bp_pose_affine(K, T, trunc) ? 1 : 0) != 0;
+}
+
+// a slot's min-bound pass: the minimum of its pixels' world points per axis into mn (folded with mn's
+// values on entry); NU pixels' loads per thread in flight.  Affine poses: the minimum of bp_world_lin and
+// the translation added once by the caller (mc_bp_world.hpp).
+template <bool kAffine, int T, int NU>
+__device__ __forceinline__ void bp_min_pass(const double *__restrict__ K, const double *__restrict__ Tp,
+                                            const double *rk, const unsigned *__restrict__ pl,
+                                            const float *__restrict__ dep, int n, int W, int t, double mn[3])
+{
+    for (int k0 = t; k0 < n; k0 += NU * T) {
+        unsigned iv[NU];
+        float dv[NU];
 #pragma unroll
-    for (int k = 0; k < 4; k++) r[k] = (((T[4 * k] * x) + (T[4 * k + 1] * y)) + (T[4 * k + 2] * z)) + T[4 * k + 3];
-    // the homogeneous divide is the identity when w == 1 (a rigid pose): skipped, bit for bit the same
-    const bool unit = r[3] == 1.0;
-    ox = unit ? r[0] : r[0] / r[3];
-    oy = unit ? r[1] : r[1] / r[3];
-    oz = unit ? r[2] : r[2] / r[3];
+        for (int u = 0; u < NU; u++) iv[u] = k0 + u * T < n ? pl[k0 + u * T] : 0u;
+#pragma unroll
+        for (int u = 0; u < NU; u++) dv[u] = k0 + u * T < n ? dep[iv[u]] : 0.f;
+#pragma unroll
+        for (int u = 0; u < NU; u++) {
+            if (k0 + u * T < n) {
+                double p[3];
+                if (kAffine)
+                    bp_world_lin(K, Tp, static_cast<int>(iv[u] % W), static_cast<int>(iv[u] / W), dv[u], p[0], p[1], p[2], rk);
+                else
+                    bp_world(K, Tp, static_cast<int>(iv[u] % W), static_cast<int>(iv[u] / W), dv[u], p[0], p[1], p[2], rk);
+#pragma unroll
+                for (int c = 0; c < 3; c++) mn[c] = fmin(mn[c], p[c]);
+            }
+        }
+    }
 }
 
 // (u3): nanoflann L2 for 3-D, ((dx*dx + dy*dy) + dz*dz)
@@ -593,6 +600,9 @@ __global__ __launch_bounds__(256) void k_bp_compact(const unsigned char *__restr
 //      barrier).  Chunks run in order, so every voxel's sum is the left fold in input order that
 //      Open3D's AccumulatedPoint makes, exactly.
 //   2. a thread per voxel: mean = sum / count
+// 0. and 1. compute the points by the affine form (no row 3 of the pose, no homogeneous divide) for a
+// slot whose frame passes bp_pose_affine, by the general form otherwise: chosen once per slot, a uniform
+// branch around two instantiations of each loop's point computation (mc_bp_world.hpp: the same bits).
 // Three barriers per chunk, no per-pixel global stores.  A slot whose voxel coordinates span >= 1024
 // voxels on an axis or that has more than V voxels is listed for the next tier (the larger LDS
 // table, then k_bp_voxel, the global-hash kernel below).
@@ -682,6 +692,7 @@ __global__ __launch_bounds__(T, WPE) void k_bp_voxel_lds(const int *__restrict__
         const unsigned *pl = pix_list + base;
         double rk[2];
         bp_recip(K, rk);
+        const bool affine = bp_slot_affine(K, Tp, pr.trunc);
         for (int i = t; i < H; i += T) {
             hkey[i] = kVxEmpty;
             hval[i] = ~0u;
@@ -691,24 +702,12 @@ __global__ __launch_bounds__(T, WPE) void k_bp_voxel_lds(const int *__restrict__
         if (t == 0) s_flag = 0;
         // 0. min bound; four pixels' loads per thread in flight
         double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-        for (int k0 = t; k0 < n; k0 += 4 * T) {
-            unsigned iv[4];
-            float dv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) iv[u] = k0 + u * T < n ? pl[k0 + u * T] : 0u;
-#pragma unroll
-            for (int u = 0; u < 4; u++) dv[u] = k0 + u * T < n ? dep[iv[u]] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                if (k0 + u * T < n) {
-                    double p[3];
-                    bp_world(K, Tp, static_cast<int>(iv[u] % W), static_cast<int>(iv[u] / W), dv[u], p[0], p[1], p[2], rk);
-#pragma unroll
-                    for (int c = 0; c < 3; c++) mn[c] = fmin(mn[c], p[c]);
-                }
-            }
-        }
+        if (affine) bp_min_pass<true, T, 4>(K, Tp, rk, pl, dep, n, W, t, mn);
+        else bp_min_pass<false, T, 4>(K, Tp, rk, pl, dep, n, W, t, mn);
         block_minmax3_nw<NW>(mn, mx, red);
+        if (affine)  // (the translation once per slot: bp_min_pass)
+#pragma unroll
+            for (int c = 0; c < 3; c++) mn[c] = mn[c] + Tp[4 * c + 3];
         BP_STAMP(36);  // 0. min bound
         double vmin[3];
 #pragma unroll
@@ -731,7 +730,8 @@ __global__ __launch_bounds__(T, WPE) void k_bp_voxel_lds(const int *__restrict__
             unsigned key = kVxEmpty;
             if (valid) {
                 double p[3];
-                bp_world(K, Tp, static_cast<int>(iv % W), static_cast<int>(iv / W), d, p[0], p[1], p[2], rk);
+                if (affine) bp_world_as<true>(K, Tp, static_cast<int>(iv % W), static_cast<int>(iv / W), d, p[0], p[1], p[2], rk);
+                else bp_world_as<false>(K, Tp, static_cast<int>(iv % W), static_cast<int>(iv / W), d, p[0], p[1], p[2], rk);
                 unsigned kk = 0;
                 bool fits = true;
 #pragma unroll
@@ -939,16 +939,15 @@ __global__ __launch_bounds__(256) void k_bp_voxel(const int *__restrict__ dNS, c
         const unsigned *pl = pix_list + base;
         double rk[2];
         bp_recip(K, rk);
+        const bool affine = bp_slot_affine(K, T, pr.trunc);
         // min bound (order-free)
         double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-        for (int k = t; k < n; k += 256) {
-            const unsigned i = pl[k];
-            double p[3];
-            bp_world(K, T, static_cast<int>(i % W), static_cast<int>(i / W), dep[i], p[0], p[1], p[2], rk);
-#pragma unroll
-            for (int c = 0; c < 3; c++) mn[c] = fmin(mn[c], p[c]);
-        }
+        if (affine) bp_min_pass<true, 256, 1>(K, T, rk, pl, dep, n, W, t, mn);
+        else bp_min_pass<false, 256, 1>(K, T, rk, pl, dep, n, W, t, mn);
         block_minmax3(mn, mx, red);
+        if (affine)  // (the translation once per slot: bp_min_pass)
+#pragma unroll
+            for (int c = 0; c < 3; c++) mn[c] = mn[c] + T[4 * c + 3];
         double vmin[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) vmin[c] = mn[c] - pr.vs * 0.5;
@@ -968,7 +967,8 @@ __global__ __launch_bounds__(256) void k_bp_voxel(const int *__restrict__ dNS, c
             unsigned e = 0;
             if (valid) {
                 const unsigned i = pl[k];
-                bp_world(K, T, static_cast<int>(i % W), static_cast<int>(i / W), dep[i], p[0], p[1], p[2], rk);
+                if (affine) bp_world_as<true>(K, T, static_cast<int>(i % W), static_cast<int>(i / W), dep[i], p[0], p[1], p[2], rk);
+                else bp_world_as<false>(K, T, static_cast<int>(i % W), static_cast<int>(i / W), dep[i], p[0], p[1], p[2], rk);
                 long long ix[3];
 #pragma unroll
                 for (int c = 0; c < 3; c++) {

@@ -1,4 +1,4 @@
-/* div_rn's identity (mc_bp_kernels.inl): for rb = RN(1 / b), RN(RN(a rb) + (a - b RN(a rb)) rb), the
+/* div_rn's identity (mc_bp_world.hpp): for rb = RN(1 / b), RN(RN(a rb) + (a - b RN(a rb)) rb), the
  * remainder exact by FMA, equals the IEEE quotient a / b (Markstein).  Checked on operands of S1's
  * per-pixel divisions (the unprojection (u - cx) z / fx, the voxel index (p - vmin) / vs, quotients
  * within a few ulps of integers where floor() is decided) and on random doubles of many exponents.
