@@ -370,6 +370,7 @@ mc::BpDev bp_make_dev(const mc_bp_params &prm, const BpKnobs &kn, int H, int W, 
     dv.rvs = 1.0 / prm.voxel_size;  // (IEEE division on the host: RN(1 / vs), div_rn's reciprocal)
     dv.eps2 = prm.dbscan_eps * prm.dbscan_eps;
     for (int i = 0; i < 3; i++) dv.knn_r2[i] = (kn.knn_fr[i] * prm.dbscan_eps) * (kn.knn_fr[i] * prm.dbscan_eps);
+    dv.knn_s = mc::knn_scale(dv.eps2);
     dv.ce = prm.dbscan_eps * 1.01;
     dv.frac = prm.component_min_fraction;
     dv.std_ratio = prm.sor_std_ratio;

@@ -21,6 +21,7 @@
 // Every per-slot array lives in the slot's pixel range [pix, pix + npix) (npix bounds every per-slot
 // count), so no allocation depends on a device result.
 #include "mc_internal.hpp"
+#include "mc_bp_knnsel.hpp"
 #include "mc_bp_qcell.hpp"
 #include "mc_bp_world.hpp"
 
@@ -37,7 +38,8 @@ constexpr unsigned long long kEmptyKey = ~0ull;
 struct BpDev {
     double trunc, vs, eps2, ce, frac, std_ratio, cov;
     double rvs;        // RN(1 / vs): the voxel index by div_rn
-    double knn_r2[3];  // k-NN pre-selection radii^2 (0.6, 0.75, 0.9 eps)
+    double knn_r2[3];  // k-NN pre-selection radii^2 (0.6, 0.75, 0.9 eps): the 16384 class's 2-bit entry classes
+    double knn_s;      // 16 / eps2: the scale of the 16 distance classes (mc_bp_knnsel.hpp), classes <= 4096
     float r2, scene_inv;
     int minpts, knn, kball, few;
     int H, W, nbands;
@@ -59,6 +61,25 @@ __device__ unsigned g_bp_slot_time[1 << 16];  // per-slot busy time (10 ns ticks
             stamp_prev = now_;                                                           \
         }                                                                                \
     } while (0)
+// the k-NN list pass's selected set of a point (0: deferred): [33] its sum over points, [31] the sum over
+// waves of the wave's largest, [32] the waves (the pass runs as long as the lane with the largest set).
+// Counted only with -DMC_BP_STAMPS_SEL beside -DMC_BP_STAMPS: the wave maximum costs the pass about as much
+// as the pass itself, so the build that counts is not the build that times.
+__device__ __forceinline__ void bp_stamp_selected(int sel)
+{
+    atomicAdd(&g_bp_stamps[33], static_cast<unsigned long long>(sel));
+    unsigned long long act = __ballot(1);
+    const int first = __ffsll(static_cast<long long>(act)) - 1;
+    int mx = 0;
+    while (act) {
+        mx = max(mx, __shfl(sel, __ffsll(static_cast<long long>(act)) - 1, 64));
+        act &= act - 1;
+    }
+    if (static_cast<int>(threadIdx.x & 63u) == first) {
+        atomicAdd(&g_bp_stamps[31], static_cast<unsigned long long>(mx));
+        atomicAdd(&g_bp_stamps[32], 1ull);
+    }
+}
 #else
 #define BP_STAMP(k) do { } while (0)
 #endif
@@ -1433,13 +1454,22 @@ __device__ __forceinline__ void lds_cells27(const BpLdsGrid &g, int x, int y, in
 // Per-workgroup eps-neighbour lists: slot k of sorted position q is the u16 at uint4 index
 // (k / 8) * N + q, half-word k % 8: a wave's stores of one k fall on 16-byte strided words (few cache
 // lines), and a point's whole list (<= 64 slots) is 8 uint4 loads issued before the first is used.
-// An entry is the neighbour's sorted position (14 bits: N <= 16384) and, in the top two bits, its
-// k-NN radius class: 0 / 1 / 2 = inside knn_r2[0 / 1 / 2] (0.6 / 0.75 / 0.9 eps), 3 = the rest of
-// the eps ball; the k-NN's candidate selection reads the classes instead of recomputing distances.
+// An entry is the neighbour's sorted position and, in the bits above it, its k-NN distance class; the
+// k-NN's candidate selection reads the classes instead of recomputing distances.  Two formats by N:
+//  * N <= 4096: 12 bits of position and four of class, one of 16 classes of equal width in d2
+//    (mc::knn_class, mc_bp_knnsel.hpp);
+//  * N = 16384: 14 bits of position and two of class: 0 / 1 / 2 = inside knn_r2[0 / 1 / 2] (0.6 / 0.75 /
+//    0.9 eps), 3 = the rest of the eps ball.
+// kNbPos<N> / kNbShift<N> decode an entry at every site that reads one (union, border labels, k-NN).
 // sflag[q] = count (bits 0-14, self included) | kept (bit 30).
 // (Measured and not kept: the near entries in a prefix region of their own, so that the k-NN of a
 // point with >= k near entries reads them with static register indices: C3 denoise +4 %, C2 +5 %.)
-constexpr unsigned kNbPos = 0x3FFFu;
+template <int N>
+constexpr bool kNbFine = N <= 4096;  // the 16-class entry format and the one-round k-NN list pass
+template <int N>
+constexpr unsigned kNbShift = kNbFine<N> ? 12u : 14u;
+template <int N>
+constexpr unsigned kNbPos = (1u << kNbShift<N>) - 1u;
 constexpr int kNbCnt = 0x7FFF;
 static_assert(kBpLdsN <= 16384, "sorted positions fit 14 bits, counts 15 bits");
 __device__ __forceinline__ int nb_cnt(int f) { return f & kNbCnt; }
@@ -1452,10 +1482,19 @@ __device__ __forceinline__ void nb_put(unsigned short *__restrict__ nbw, int q, 
                          (static_cast<unsigned>(k) & 7u);
     *reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(nbw) + (off << 1)) = static_cast<unsigned short>(e);
 }
+template <int N>
 __device__ __forceinline__ unsigned nb_class(double d2, const BpDev &pr)
 {
-    return 3u - (d2 < pr.knn_r2[0] ? 1u : 0u) - (d2 < pr.knn_r2[1] ? 1u : 0u) - (d2 < pr.knn_r2[2] ? 1u : 0u);
+    if constexpr (kNbFine<N>) return mc::knn_class(d2, pr.knn_s);
+    else return 3u - (d2 < pr.knn_r2[0] ? 1u : 0u) - (d2 < pr.knn_r2[1] ? 1u : 0u) - (d2 < pr.knn_r2[2] ? 1u : 0u);
 }
+// the union's sampled far links (step 6) by class: farA takes the outer part of the eps ball (d >= 0.9 eps:
+// class 3 of the 2-bit format, classes 13 .. 15 of the 16), farB the ring inside it (0.75 .. 0.9 eps:
+// class 2, classes 9 .. 12)
+template <int N>
+__device__ __forceinline__ bool nb_far_a(unsigned c) { return kNbFine<N> ? c >= 13u : c == 3u; }
+template <int N>
+__device__ __forceinline__ bool nb_far_b(unsigned c) { return kNbFine<N> ? c - 9u <= 3u : c == 2u; }
 
 // The list builders' walk over the records of ranges d0 .. 26 (range(d, key): the bucket range of
 // cell d and its key), flat: a lane goes through the records of its non-empty ranges in one loop,
@@ -1507,8 +1546,8 @@ __device__ __forceinline__ void lds_flat_walk(const BpLdsGrid &g, int d0, Range 
 // the record loaded whole).  The entries are packed in registers (mc::NbPack, mc_bp_nbpack.hpp) and
 // leave as whole 16-byte words: one store per eight entries, and the last, partial word after the
 // walk with its unused half-words zero.  Entries past kBpNbCap are counted and not stored (the list
-// is unused then: the point walks its cells).  farA / farB: the last neighbour of radius class 3 / 2
-// (the union's sampled links, step 6).  Returns the count.
+// is unused then: the point walks its cells).  farA / farB: the last neighbour of the two outer distance
+// ranges (nb_far_a / nb_far_b: the union's sampled links, step 6).  Returns the count.
 // (Measured and not kept, docs/experiments.md "own-walk lists": this builder in the 512 .. 3072
 // classes instead of the pair pass: C3 denoise +15 %, C2 +11 %; it tests twice the candidates, and
 // the pair pass's LDS atomics and 2-byte stores cost less than those tests.)
@@ -1540,10 +1579,10 @@ __device__ __forceinline__ int lds_eps_own(const BpLdsGrid &g, int x, int y, int
         const double dx = ax - p.x, dy = ay - p.y, dz = az - p.z;
         const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
         if (static_cast<unsigned long long>(__double_as_longlong(p.w)) == key && d2 < eps2) {  // (no kept bits yet)
-            const unsigned c = nb_class(d2, pr);
-            acc.push(static_cast<unsigned>(q2) | (c << 14));
-            fa = c == 3u ? q2 : fa;
-            fb = c == 2u ? q2 : fb;
+            const unsigned c = nb_class<N>(d2, pr);
+            acc.push(static_cast<unsigned>(q2) | (c << kNbShift<N>));
+            fa = nb_far_a<N>(c) ? q2 : fa;
+            fb = nb_far_b<N>(c) ? q2 : fb;
             cnt++;
             if (mc::nb_store_full(cnt, kBpNbCap)) put(acc, cnt);
         }
@@ -1596,15 +1635,15 @@ __device__ __forceinline__ void lds_eps_pairs(const BpLdsGrid &g, int x, int y, 
         const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
         // (no record carries the kept bit yet: the class filter sets it after the lists are built)
         if (static_cast<unsigned long long>(__double_as_longlong(p.w)) == key && d2 < eps2) {
-            // both slots' atomics in flight together; the radius class and the far links (radius
-            // classes 3 and 2 of this point's forward walk: the union's sampled links, step 6, stored
+            // both slots' atomics in flight together; the distance class and the far links (the two outer
+            // distance ranges of this point's forward walk: the union's sampled links, step 6, stored
             // once after the walk) computed under them; one wait before the stores.  Entries past
             // the cap overwrite the last slot: every slot still holds a neighbour,
             // and a list past the cap is not read (its point walks the cells), so no branch
             const int o1 = atomicAdd(&sflag[q], 1), o2 = atomicAdd(&sflag[q2], 1);
-            const unsigned c = nb_class(d2, pr) << 14;
-            fa = c == (3u << 14) ? q2 : fa;
-            fb = c == (2u << 14) ? q2 : fb;
+            const unsigned c0 = nb_class<N>(d2, pr), c = c0 << kNbShift<N>;
+            fa = nb_far_a<N>(c0) ? q2 : fa;
+            fb = nb_far_b<N>(c0) ? q2 : fb;
             asm volatile("" ::"v"(o1), "v"(o2), "v"(c));
             nb_put<N>(nbw, q, min(o1, kBpNbCap - 1), static_cast<unsigned>(q2) | c);
             nb_put<N>(nbw, q2, min(o2, kBpNbCap - 1), static_cast<unsigned>(q) | c);
@@ -1726,7 +1765,7 @@ MC_DBG_FN void bp_dbg_lists(const BpLdsGrid &g, const int *sflag, const unsigned
         unsigned long long sum = 0, xr = 0;
         lds_cells27(g, x, y, z, 0ull, a.x, a.y, a.z, [&](int q2, double d2) {
             if (d2 < pr.eps2) {
-                const unsigned long long e = static_cast<unsigned>(q2) | (nb_class(d2, pr) << 14);
+                const unsigned long long e = static_cast<unsigned>(q2) | (nb_class<N>(d2, pr) << kNbShift<N>);
                 c++;
                 sum += bp_dbg_mix(e);
                 xr ^= bp_dbg_mix(e + 0x51ED2701ull);
@@ -2033,7 +2072,7 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
             // minpts >= 2 (DBSCAN's 4 here): with minpts 1 a one-entry own-walk list would give its zero
             // padding, position 0, and a pair list a stale slot
             const uint4 w0 = reinterpret_cast<const uint4 *>(nbw)[q];
-            const int cand[3] = {static_cast<int>(((w0.x >> 16) & 0xFFFFu) & kNbPos), sX[q], slab[q]};
+            const int cand[3] = {static_cast<int>(((w0.x >> 16) & 0xFFFFu) & kNbPos<N>), sX[q], slab[q]};
 #pragma unroll
             for (int r = 0; r < 3; r++) {
                 const int q2 = cand[r];
@@ -2076,11 +2115,11 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
                 // read early is still a node of q2's component, so it is a valid place to start the find)
                 nb_walk(w, cnt,
                         [&](unsigned e) {
-                            const int q2 = static_cast<int>(e & kNbPos);
+                            const int q2 = static_cast<int>(e & kNbPos<N>);
                             return make_int2(sflag[q2], ld_wg(spar + q2));
                         },
                         [&](int, unsigned e, int2 fp) {
-                            const int q2 = static_cast<int>(e & kNbPos);
+                            const int q2 = static_cast<int>(e & kNbPos<N>);
                             if (q2 != q && nb_cnt(fp.x) >= pr.minpts && fp.y != ra) {  // parent == root: joined already
                                 const int rb = uf_find_s(spar, fp.y);
                                 if (rb != ra) {
@@ -2165,7 +2204,7 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
                 if (cnt <= pr.nbcap) {
                     nb_load<N>(nbw, q, cnt, w);
                     nb_walk(w, cnt, [](unsigned e) { return e; },
-                            [&](int, unsigned e, unsigned) { near(static_cast<int>(e & kNbPos)); });
+                            [&](int, unsigned e, unsigned) { near(static_cast<int>(e & kNbPos<N>)); });
                 } else {
                     int x, y, z;
                     unpack3(keyof(q), x, y, z);
@@ -2234,34 +2273,72 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
                 sring[atomicAdd(&s_ndef, 1)] = q;
                 continue;
             }
-            double best[kBpKnnMax];
+            // the k smallest squared distances, ascending, in the first k elements (the 16-class formats:
+            // the sorting network's whole array, no list beside it)
+            double best[kNbFine<N> ? mc::kKnnNet : kBpKnnMax];
             const double4 a = spt[q];
             auto d2of = [&](const double4 &p) {
                 const double ex = a.x - p.x, ey = a.y - p.y, ez = a.z - p.z;
                 return ((ex * ex) + (ey * ey)) + (ez * ez);
             };
+            // selection pass: pm = the kept candidates the k nearest are among (bit k = slot k), from the
+            // entries' distance classes: if >= k kept entries have a class <= c*, every other kept
+            // candidate is at least as far as all of them, so only those are sorted.  Kept flags (bit 30
+            // of sflag, the next one loaded ahead) are read only when the class filter dropped points.
+            unsigned long long pm = 0, mall = 0;
+            if constexpr (!kNbFine<N>) {
 #pragma unroll
-            for (int k = 0; k < kBpKnnMax; k++) best[k] = DBL_MAX;
-            // selection pass: the kept candidates inside three radii (bit k of m1 / m2 / m3 = slot k),
-            // from the entries' radius classes; if >= k of them lie inside radius i, the k nearest are
-            // among those (every other kept candidate is farther than >= k others), so only they are
-            // inserted: each lane walks its own mask, and the wave's insert loop runs max-over-lanes
-            // of ~k + a few instead of the largest list.  Kept flags (bit 30 of sflag, the next one
-            // loaded ahead) are read only when the class filter dropped points.
-            unsigned long long m1 = 0, m2 = 0, m3 = 0, mall = 0;
+                for (int k = 0; k < kBpKnnMax; k++) best[k] = DBL_MAX;
+            }
             nb_load<N>(nbw, q, cnt, w);
-            nb_walk(w, cnt, [&](unsigned e) { return all_kept ? 1 << 30 : sflag[e & kNbPos]; },
-                    [&](int k, unsigned e, int f) {
-                        const unsigned long long bit = (f & (1 << 30)) ? 1ull << k : 0ull;
-                        const unsigned c = e >> 14;
-                        mall |= bit;
-                        m1 |= c == 0u ? bit : 0ull;
-                        m2 |= c <= 1u ? bit : 0ull;
-                        m3 |= c <= 2u ? bit : 0ull;
-                    });
+            auto kept_of = [&](unsigned e) { return all_kept ? 1 << 30 : sflag[e & kNbPos<N>]; };
+            if constexpr (kNbFine<N>) {
+                // 16 classes: a histogram of the kept entries' classes gives the smallest c* that k of
+                // them reach (mc_bp_knnsel.hpp); a second walk over the register words collects them
+                mc::KnnHist hist;
+                nb_walk(w, cnt, kept_of, [&](int k, unsigned e, int f) {
+                    const unsigned on = (static_cast<unsigned>(f) >> 30) & 1u;
+                    mall |= static_cast<unsigned long long>(on) << k;
+                    hist.add(e >> kNbShift<N>, on);
+                });
+                const int cstar = mc::knn_threshold(hist, kk);  // -1: fewer than k kept entries
+                nb_walk(w, cnt, [](unsigned e) { return e; }, [&](int k, unsigned e, unsigned) {
+                    pm |= static_cast<int>(e >> kNbShift<N>) <= cstar ? 1ull << k : 0ull;
+                });
+                pm &= mall;
+            } else {
+                // three radii (m1 / m2 / m3): the smallest of the nested sets that holds k
+                unsigned long long m1 = 0, m2 = 0, m3 = 0;
+                nb_walk(w, cnt, kept_of, [&](int k, unsigned e, int f) {
+                    const unsigned long long bit = (f & (1 << 30)) ? 1ull << k : 0ull;
+                    const unsigned c = e >> kNbShift<N>;
+                    mall |= bit;
+                    m1 |= c == 0u ? bit : 0ull;
+                    m2 |= c <= 1u ? bit : 0ull;
+                    m3 |= c <= 2u ? bit : 0ull;
+                });
+                pm = __popcll(m1) >= kk ? m1 : __popcll(m2) >= kk ? m2 : __popcll(m3) >= kk ? m3 : mall;
+            }
             const int found = __popcll(mall);
-            unsigned long long pm = __popcll(m1) >= kk ? m1 : __popcll(m2) >= kk ? m2 : __popcll(m3) >= kk ? m3 : mall;
-            if (found >= kk) {
+#ifdef MC_BP_STAMPS
+            // (every point of the pass, the deferred ones included, in both entry formats)
+            atomicAdd(&g_bp_stamps[29], static_cast<unsigned long long>(found));
+            atomicAdd(&g_bp_stamps[13], 1ull);
+#endif
+#ifdef MC_BP_STAMPS_SEL
+            bp_stamp_selected(found >= kk ? __popcll(pm) : 0);
+#endif
+            if constexpr (kNbFine<N>) {
+                // fewer than k kept entries: the ring queue's.  The 16-class format leaves here, before the
+                // array is written: an array that reaches the sum below undefined on one path and sorted on
+                // the other cost the pass spills inside this loop.  (The 2-bit format defers after its
+                // insert loop, below, as it always did.)
+                if (found < kk) {
+                    sring[atomicAdd(&s_ndef, 1)] = q;
+                    continue;
+                }
+            }
+            if (kNbFine<N> || found >= kk) {  // (16-class format: always, found >= kk from here on)
                 // slot k of q: byte (((k / 8) * N + q) * 8 + k % 8) * 2 of the region (32-bit offsets
                 // from the workgroup's base, as nb_put)
                 const char *lstb = reinterpret_cast<const char *>(nbw);
@@ -2280,27 +2357,73 @@ __global__ __launch_bounds__(BpLdsClass<N>::T, BpLdsClass<N>::kWgPerCu * BpLdsCl
                         e[u] = b >= 0 ? static_cast<int>(*reinterpret_cast<const unsigned short *>(lstb + ob)) : -1;
                     }
                 };
-                int en[kBpKnnBatch];
-                fetch(en);
-                while (en[0] >= 0) {
-                    double d2[kBpKnnBatch];
+                if constexpr (kNbFine<N>) {
+                    // one round: the first kKnnNet selected entries, every load issued before the first
+                    // use (a selected set is 20 .. ~24 entries: no trip loop whose length is the wave's
+                    // largest set, no chain of dependent reloads).  An absent entry reads slot 0 (a valid
+                    // address: every list holds its point) and is marked -1: no branch around a load.
+                    int en[mc::kKnnNet];
 #pragma unroll
-                    for (int u = 0; u < kBpKnnBatch; u++) {
-                        const double4 p = spt[en[u] >= 0 ? en[u] & kNbPos : q];
-                        d2[u] = en[u] >= 0 ? d2of(p) : DBL_MAX;
+                    for (int u = 0; u < mc::kKnnNet; u++) {
+                        const unsigned b = pm ? static_cast<unsigned>(__ffsll(static_cast<long long>(pm)) - 1) : 0u;
+                        const unsigned ob = (b >> 3) * (16u * static_cast<unsigned>(N)) + qb + ((b & 7u) << 1);
+                        const int e = static_cast<int>(*reinterpret_cast<const unsigned short *>(lstb + ob));
+                        en[u] = pm ? e : -1;
+                        pm &= pm - 1;
                     }
-                    fetch(en);
+                    // their squared distances straight into the sorting network's array, DBL_MAX for the
+                    // absent ones; the network leaves the array's first k elements the k smallest, ascending
 #pragma unroll
-                    for (int u = 0; u < kBpKnnBatch; u++) sorted_insert(best, d2[u]);
+                    for (int u = 0; u < mc::kKnnNet; u++) {
+                        const double v = d2of(spt[en[u] >= 0 ? en[u] & kNbPos<N> : q]);
+                        best[u] = en[u] >= 0 ? v : DBL_MAX;
+                    }
+                    mc::knn_net_sort(best, [](double &lo, double &hi) {
+                        const double x = lo, y = hi;
+                        lo = ins_min(x, y);
+                        hi = ins_max(x, y);
+                    });
+                    // leftovers (a set larger than the network, rare): the batched insert loop on the
+                    // sorted first k, entered only if some lane of the wave has any
+                    if (__ballot(pm != 0ull)) {
+                        int el[kBpKnnBatch];
+                        fetch(el);
+                        while (el[0] >= 0) {
+                            double d2[kBpKnnBatch];
+#pragma unroll
+                            for (int u = 0; u < kBpKnnBatch; u++) {
+                                const double4 p = spt[el[u] >= 0 ? el[u] & kNbPos<N> : q];
+                                d2[u] = el[u] >= 0 ? d2of(p) : DBL_MAX;
+                            }
+                            fetch(el);
+#pragma unroll
+                            for (int u = 0; u < kBpKnnBatch; u++)
+                                mc::knn_insert<kBpKnnMax>(
+                                    best, d2[u], [](double x, double y) { return ins_min(x, y); },
+                                    [](double x, double y) { return ins_max(x, y); });
+                        }
+                    }
+                } else {
+                    int en[kBpKnnBatch];
+                    fetch(en);
+                    while (en[0] >= 0) {
+                        double d2[kBpKnnBatch];
+#pragma unroll
+                        for (int u = 0; u < kBpKnnBatch; u++) {
+                            const double4 p = spt[en[u] >= 0 ? en[u] & kNbPos<N> : q];
+                            d2[u] = en[u] >= 0 ? d2of(p) : DBL_MAX;
+                        }
+                        fetch(en);
+#pragma unroll
+                        for (int u = 0; u < kBpKnnBatch; u++) sorted_insert(best, d2[u]);
+                    }
                 }
             }
-#ifdef MC_BP_STAMPS
-            atomicAdd(&g_bp_stamps[29], static_cast<unsigned long long>(found));
-            atomicAdd(&g_bp_stamps[13], 1ull);
-#endif
-            if (found < kk) {
-                sring[atomicAdd(&s_ndef, 1)] = q;
-                continue;
+            if constexpr (!kNbFine<N>) {  // (the 16-class format deferred these points above)
+                if (found < kk) {
+                    sring[atomicAdd(&s_ndef, 1)] = q;
+                    continue;
+                }
             }
             double sum = 0.0;
 #pragma unroll

@@ -49,10 +49,15 @@ for off, kern in ((16, "k_bp_denoise_lds"), (0, "k_bp_denoise (large slots)")):
         print(f"  {n:12s} {100.0 * v / max(tot, 1):6.2f} % {per}")
 print("k-NN sub-phases us/slot: main list pass", round(float(buf[34]) / 100.0 / nslots, 2), "ring search",
       round(float(buf[35]) / 100.0 / nslots, 2), "whole-cloud fallback", round(float(buf[26]) / 100.0 / nslots, 2))
-print("k-NN points deferred to the ring search", int(buf[30]), "(list overflow", int(buf[32]), "/ < k kept in the list",
-      int(buf[33]), ")", "near-tied keys redone exactly", int(buf[31]))
-print("knn points", int(buf[13]), "candidates/point", round(float(buf[29]) / max(int(buf[13]), 1), 1),
-      "fallbacks", int(buf[31]))
+print("k-NN points deferred to the ring search", int(buf[30]))
+# the list pass's selected set (the entries a point fetches and sorts): its mean over the pass's points (the
+# deferred ones count as 0), and the mean over waves of the wave's largest
+print("knn points", int(buf[13]), "candidates/point", round(float(buf[29]) / max(int(buf[13]), 1), 1))
+if int(buf[32]):  # counted only by a build with -DMC_BP_STAMPS_SEL
+    print("selected/point", round(float(buf[33]) / max(int(buf[13]), 1), 2), "wave max selected",
+          round(float(buf[31]) / max(int(buf[32]), 1), 2), "over", int(buf[32]), "waves")
+else:
+    print("selected-set counters off (build with -DMC_BP_STAMPS -DMC_BP_STAMPS_SEL to count them)")
 vt = [float(buf[k]) for k in (36, 38, 40, 37, 39)]
 vtot = max(sum(vt), 1.0)
 print("k_bp_voxel_lds workgroup-busy shares:", {n: f"{100 * v / vtot:.1f} %" for n, v in
