@@ -129,6 +129,31 @@ def s1_frames(scene_f32, depth, seg, K, poses, params: BpParams | None = None, t
     return out
 
 
+def s1_voxel(points, voxel_size=0.01):
+    """the oracle's voxel_down_sample alone: float64 [n, 3] -> the voxel means [nv, 3], first-occurrence order"""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    out = np.zeros_like(p)
+    nv = lib().orc_s1_voxel(p.reshape(-1), len(p), float(voxel_size), out.reshape(-1))
+    return out[:nv].copy()
+
+
+def s1_dbscan(points, eps=0.04, min_points=4):
+    """the oracle's cluster_dbscan alone: float64 [n, 3] -> labels int32 [n] (-1 = noise)"""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    labels = np.zeros(len(p), np.int32)
+    lib().orc_s1_dbscan(p.reshape(-1), len(p), float(eps), int(min_points), labels)
+    return labels
+
+
+def s1_sor(points, idx, nb_neighbors=20, std_ratio=2.0):
+    """the oracle's remove_statistical_outlier alone on the points idx of float64 [n, 3] -> keep flags [len(idx)]"""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    idx = np.ascontiguousarray(idx, np.int32)
+    keep = np.zeros(max(len(idx), 1), np.uint8)
+    lib().orc_s1_sor(p.reshape(-1), idx, len(idx), int(nb_neighbors), float(std_ratio), keep)
+    return keep[:len(idx)].astype(bool)
+
+
 class threads:
     """``with oracle.threads(n):`` runs the OpenMP loops of the S2-S6 oracle on n threads"""
 
@@ -228,6 +253,12 @@ def lib():
         L.orc_s1_frame.argtypes = [ctypes.c_int64, _f32p, ctypes.c_int, ctypes.c_int, _f32p, _u8p, _f64p, _f64p,
                                    ctypes.POINTER(BpParams), _i32p, _i64p, _i32p, ctypes.c_int64,
                                    ctypes.POINTER(ctypes.c_int64), _i32p, ctypes.POINTER(ctypes.c_int32)]
+        L.orc_s1_voxel.restype = ctypes.c_int
+        L.orc_s1_voxel.argtypes = [_f64p, ctypes.c_int, ctypes.c_double, _f64p]
+        L.orc_s1_dbscan.restype = None
+        L.orc_s1_dbscan.argtypes = [_f64p, ctypes.c_int, ctypes.c_double, ctypes.c_int, _i32p]
+        L.orc_s1_sor.restype = ctypes.c_int
+        L.orc_s1_sor.argtypes = [_f64p, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _u8p]
         _lib = L
     return _lib
 

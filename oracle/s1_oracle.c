@@ -28,6 +28,15 @@
  *        d2 = fmaf(dz, dz, fmaf(dy, dy, dx*dx)); radius2 = float(r) * float(r).
  * Output sets are order-free; (u2) only matters at DBSCAN border ties and in the
  * last bits of the outlier statistics.
+ *
+ * What checks this restatement: tests/s1_witness.py (numpy, longdouble, written from the
+ * reference's Python and the published algorithms, not from this file) must agree frame by
+ * frame and, through orc_s1_voxel / orc_s1_dbscan / orc_s1_sor below, label by label and keep
+ * flag by keep flag, on inputs without knife-edge decisions; scikit-learn's DBSCAN and scipy's
+ * cKDTree must agree with the witness (tests/test_s1_witness_cpu.py).  That checks the
+ * algorithms (DBSCAN labels with their border assignments, the class filter, the k-NN means
+ * and the threshold, the ball sets).  It cannot pin (u1)-(u4): the libraries' own rounding
+ * order and container order.
  */
 #include <math.h>
 #include <stdint.h>
@@ -444,4 +453,21 @@ void orc_s1_batch_take(void *hp, int32_t *pts)
     free(h->pts);
     free(h->np);
     free(h);
+}
+
+/* ---- the library restatements one at a time, for the per-stage comparison with the independent
+ * witness (tests/s1_witness.py, tests/test_s1_witness_cpu.py): thin wrappers, no logic of their own ---- */
+int orc_s1_voxel(const double *pts, int n, double voxel_size, double *out)
+{
+    return n > 0 ? voxel_down(pts, n, voxel_size, out) : 0;
+}
+
+void orc_s1_dbscan(const double *p, int n, double eps, int min_points, int32_t *labels)
+{
+    dbscan(p, n, eps, min_points, labels);
+}
+
+int orc_s1_sor(const double *p, const int32_t *idx, int m, int nb_neighbors, double std_ratio, uint8_t *keep)
+{
+    return statistical_outlier(p, idx, m, nb_neighbors, std_ratio, keep);
 }
