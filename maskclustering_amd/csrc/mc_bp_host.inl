@@ -54,13 +54,10 @@ size_t slots_cap(int fb) { return static_cast<size_t>(fb) * 256 + 1; }  // (fram
 #endif
 constexpr int kBpOversub = MC_BP_OVERSUB;  // class grids: resident workgroups x this (slots come from tickets)
 
-// The capacities of the denoise's LDS size classes, ascending: the host side's one list (class index
-// = position).  mc::BpLdsClass<N> gives each class's shape; k_bp_classify's thresholds in
-// mc_bp_kernels.inl repeat the list (kernel code, kept as compiled) and must agree with it.
-constexpr int kBpClassN[] = {512, 1024, 2048, 3072, 4096, 16384};
-static_assert(sizeof(kBpClassN) / sizeof(kBpClassN[0]) == mc::kBpClasses && mc::kBpClasses == mc::kBpStreamClasses + 1,
-              "one entry per LDS class; every class but the last has a stream of its own");
-static_assert(kBpClassN[mc::kBpClasses - 1] == mc::kBpLdsN, "the last class is the LDS kernel's largest");
+// The capacities of the denoise's LDS size classes, ascending (class index = position): mc::kBpClassN
+// (mc_bp_denoise_lds.inl), the list k_bp_classify's thresholds read too.  mc::BpLdsClass<N> gives each
+// class's shape.
+using mc::kBpClassN;
 constexpr int bp_class_index(int N)
 {
     for (int c = 0; c < mc::kBpClasses; c++)

@@ -1,5 +1,5 @@
 // mc_bp_knnsel.hpp — S1 denoise: the k-NN list pass's candidate selection in the LDS classes of up to
-// 4096 points (k_bp_denoise_lds, mc_bp_kernels.inl, step 10).  Plain C++17 without a HIP include, usable
+// 4096 points (k_bp_denoise_lds, mc_bp_denoise_lds.inl, step 10).  Plain C++17 without a HIP include, usable
 // from host and device; scripts/bp_knnsel_check.cpp checks it on the CPU (tests/test_bp_knnsel_cpu.py).
 //  * knn_class(d2, s) is the distance class of an eps-list entry, 0 .. 15, stored in the entry's top four
 //    bits: min(15, (unsigned)(d2 * s)) with s = 16 / eps2 (knn_scale, computed once on the host).  It is a

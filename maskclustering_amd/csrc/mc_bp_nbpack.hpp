@@ -1,8 +1,8 @@
 // mc_bp_nbpack.hpp — S1 denoise: how the entries of an eps-neighbour list reach their 16-byte words.
 // Plain C++17 without a HIP include, usable from host and device: the own-walk list builder of the LDS
-// denoise classes (lds_eps_own, mc_bp_kernels.inl) packs with it, every class reads slots with it
+// denoise classes (lds_eps_own, mc_bp_denoise_lds.inl) packs with it, every class reads slots with it
 // (nb_ent), and scripts/bp_nbpack_check.cpp checks it on the CPU (tests/test_bp_nbpack_cpu.py).
-// The layout (mc_bp_kernels.inl, "Per-workgroup eps-neighbour lists"): slot k of sorted position q is
+// The layout (mc_bp_denoise_lds.inl, "Per-workgroup eps-neighbour lists"): slot k of sorted position q is
 // half-word k % 8 of the 16-byte word (k / 8) * N + q; the low half of a 32-bit register is the even slot.
 //  * NbPack holds the word being filled in four 32-bit registers.  push() shifts the whole 128 bits
 //    down by one half-word and puts the new entry on top, so after eight pushes entry j of the word

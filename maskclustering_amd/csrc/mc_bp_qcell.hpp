@@ -1,6 +1,6 @@
 // mc_bp_qcell.hpp — S1 ball query: the cell arithmetic of a slot's box on the 2r scene grid.
 // Plain C++17 without a HIP include, usable from host and device: k_grid_count builds the scene grid with
-// scene_cell, k_bp_query_lds (mc_bp_kernels.inl) enumerates the cells of a mask's float32 AABB and
+// scene_cell, k_bp_query_lds (mc_bp_query.inl) enumerates the cells of a mask's float32 AABB and
 // numbers them with these functions, and scripts/bp_qcell_check.cpp checks them on the CPU
 // (tests/test_bp_qcell_cpu.py).
 //  * scene_cell(v, inv) is the biased cell coordinate of v on a grid of cell width 1 / inv, clamped to

@@ -1,6 +1,6 @@
 // mc_bp_world.hpp — S1 voxels: a mask pixel's world point (Open3D create_from_depth_image + transform, in
 // double, no FMA but div_rn's own; oracle/s1_oracle.c (a1), (u1)).
-// Plain C++17 without a HIP include, usable from host and device: the voxel kernels (mc_bp_kernels.inl)
+// Plain C++17 without a HIP include, usable from host and device: the voxel kernels (mc_bp_voxel.inl)
 // compute every pixel's point with these functions, and scripts/bp_world_check.cpp checks them on the CPU
 // (tests/test_bp_world_cpu.py).  Build with -ffp-contract=off: every operation is rounded where it stands.
 //  * div_rn(a, b, rb) is a / b rounded to nearest from rb = RN(1 / b) (Markstein: q0 = RN(a rb),

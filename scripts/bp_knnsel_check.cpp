@@ -1,6 +1,6 @@
 // S1 denoise k-NN candidate selection (maskclustering_amd/csrc/mc_bp_knnsel.hpp) on the CPU: the distance
 // class, the class histogram's threshold, the sorting network, and the whole selection written as step 10 of
-// k_bp_denoise_lds (mc_bp_kernels.inl) is, against std::sort.  Built and run by tests/test_bp_knnsel_cpu.py:
+// k_bp_denoise_lds (mc_bp_denoise_lds.inl) is, against std::sort.  Built and run by tests/test_bp_knnsel_cpu.py:
 //   g++ -std=c++17 -O1 -g -Wall -Werror -ffp-contract=off -fsanitize=address,undefined -I maskclustering_amd/csrc
 //       scripts/bp_knnsel_check.cpp -o bp_knnsel_check && ./bp_knnsel_check
 #include <algorithm>

@@ -1,5 +1,5 @@
 // S1 denoise list packing (maskclustering_amd/csrc/mc_bp_nbpack.hpp) on the CPU: a list builder written
-// as lds_eps_own (mc_bp_kernels.inl) is, run for every count 0 .. 66 and read back as nb_load / nb_ent
+// as lds_eps_own (mc_bp_denoise_lds.inl) is, run for every count 0 .. 66 and read back as nb_load / nb_ent
 // read it.  Built and run by tests/test_bp_nbpack_cpu.py:
 //   g++ -std=c++17 -O1 -g -Wall -Werror -fsanitize=address,undefined -I maskclustering_amd/csrc
 //       scripts/bp_nbpack_check.cpp -o bp_nbpack_check && ./bp_nbpack_check

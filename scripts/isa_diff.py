@@ -3,7 +3,11 @@
 §4, round-4 investigation), so a source change is validated against the GPU runs of the build whose
 code it reproduces: an unchanged kernel list means the tested machine code ships.
 
-    python scripts/isa_diff.py <git-rev> [kernel-substring]   # <git-rev>'s source against the working tree
+    python scripts/isa_diff.py <git-rev> [kernel-substring] [-DNAME[=VALUE] ...]
+
+compares <git-rev>'s source with the working tree; the -D arguments go to both compiles (the diagnostics
+and stamps builds).  Only symbols the assembly types as functions are compared.  Exit status 1 when any
+function differs or exists on one side only.
 """
 import os
 import re
@@ -15,12 +19,15 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--offload-device-only"]
 
 
-def device_asm(src_dir, out):
-    subprocess.check_call(["/opt/rocm/bin/hipcc", *FLAGS, os.path.join(src_dir, "mc_api.hip"), "-o", out],
+def device_asm(src_dir, out, defines):
+    subprocess.check_call(["/opt/rocm/bin/hipcc", *FLAGS, *defines, os.path.join(src_dir, "mc_api.hip"), "-o", out],
                           stderr=subprocess.DEVNULL)
     s = open(out).read()
+    is_func = set(re.findall(r"^\s*\.type\s+(\S+),@function", s, re.M))
     funcs = {}
     for m in re.finditer(r"^(_ZN2mc[^\s:]*):", s, re.M):
+        if m.group(1) not in is_func:
+            continue
         end = s.find(".Lfunc_end", m.end())
         funcs[m.group(1)] = [l for l in s[m.end():end].splitlines()
                              if l.strip() and not l.strip().startswith((".loc", ";", ".Ltmp", ".cfi"))]
@@ -28,22 +35,25 @@ def device_asm(src_dir, out):
 
 
 def main():
-    rev = sys.argv[1]
-    sub = sys.argv[2] if len(sys.argv) > 2 else "k_bp"
+    defines = [a for a in sys.argv[1:] if a.startswith("-D")]
+    args = [a for a in sys.argv[1:] if not a.startswith("-D")]
+    rev = args[0]
+    sub = args[1] if len(args) > 1 else "k_bp"
     with tempfile.TemporaryDirectory() as tmp:
         wt = os.path.join(tmp, "wt")
         subprocess.check_call(["git", "-C", REPO, "worktree", "add", "-f", "-q", wt, rev])
         try:
-            a = device_asm(os.path.join(wt, "maskclustering_amd", "csrc"), os.path.join(tmp, "a.s"))
+            a = device_asm(os.path.join(wt, "maskclustering_amd", "csrc"), os.path.join(tmp, "a.s"), defines)
         finally:
             subprocess.call(["git", "-C", REPO, "worktree", "remove", "--force", wt])
-        b = device_asm(os.path.join(REPO, "maskclustering_amd", "csrc"), os.path.join(tmp, "b.s"))
+        b = device_asm(os.path.join(REPO, "maskclustering_amd", "csrc"), os.path.join(tmp, "b.s"), defines)
     names = sorted(k for k in set(a) | set(b) if sub in k)
     diff = [k for k in names if a.get(k) != b.get(k)]
     for k in diff:
         print("differs:", k, len(a.get(k, [])), len(b.get(k, [])))
     print(f"{len(names) - len(diff)} of {len(names)} kernels matching '{sub}' identical")
+    return 1 if diff else 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

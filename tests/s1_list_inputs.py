@@ -12,7 +12,7 @@ from conftest import GOLDEN
 
 NBCAPS = [7, 8, 9, 16, 17, 64]
 MIN_CLASSES = [0, 2, 4, 5, 6]
-CLASS_N = [512, 1024, 2048, 3072, 4096, 16384]  # kBpClassN (mc_bp_host.inl): the LDS classes' capacities
+CLASS_N = [512, 1024, 2048, 3072, 4096, 16384]  # mc::kBpClassN (mc_bp_denoise_lds.inl): the LDS classes' capacities
 
 
 def dense_inputs():

@@ -24,7 +24,7 @@ CELL_BIAS = 1 << 20
 # slot of these inputs is as small as 64 cells)
 SPLIT_CAND = 200
 SPLIT_CELLS = 640
-DEFAULT_CAND, DEFAULT_CELLS = 1024, 4096  # kBpQcCand, kBpQcCells (mc_bp_kernels.inl)
+DEFAULT_CAND, DEFAULT_CELLS = 1024, 4096  # kBpQcCand, kBpQcCells (mc_bp_query.inl)
 # parameter sets under which the first-K rule binds (ball_k below the in-ball count of some point)
 FIRSTK = [dict(ball_k=1), dict(ball_k=7), dict(ball_radius=0.03, ball_k=20)]
 QUANT = 0.005

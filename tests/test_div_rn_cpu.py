@@ -1,4 +1,4 @@
-"""div_rn (maskclustering_amd/csrc/mc_bp_kernels.inl): S1's per-pixel divisions (the unprojection by
+"""div_rn (maskclustering_amd/csrc/mc_bp_world.hpp): S1's per-pixel divisions (the unprojection by
 fx / fy, the voxel index by the voxel size) are a reciprocal multiply and two FMAs whose result must be
 the IEEE quotient bit for bit, since the voxel partition and the voxel means are Open3D's exact
 arithmetic (oracle/s1_oracle.c divides).  The identity (Markstein) is checked here on

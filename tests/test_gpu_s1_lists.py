@@ -1,4 +1,4 @@
-"""S1 denoise eps-neighbour lists at their word and cap boundaries (mc_bp_kernels.inl: a list is eight 16-byte
+"""S1 denoise eps-neighbour lists at their word and cap boundaries (mc_bp_denoise_lds.inl: a list is eight 16-byte
 words of eight u16 entries; lds_eps_pairs fills them entry by entry at slots its LDS atomics return,
 lds_eps_own stores whole words of eight, a partial last word after the walk and nothing past the cap of 64):
 MC_BP_NBCAP at 7 / 8 / 9 (the first word's flush), 16 / 17 (a later one) and 64 (the cap), crossed with
