@@ -541,6 +541,52 @@ int mc_crop_render(mc_ctx *ctx, int32_t num_frames, int32_t H, int32_t W, const 
                    int boxes_on_device, const mc_crop_params *params, float *out);
 int mc_crop_coeffs(mc_ctx *ctx, int32_t in_size, int32_t out_size, int32_t *ksize, int32_t *bounds, int32_t *kk);
 
+/* ---- projected boxes of the objects' top views ---------------------------------------------------
+ * Replaces get_bbox_by_projection (get_top_images.py:180-237), the reference's only world -> image
+ * projection: a request (object, frame) projects the object's points into the frame's camera and
+ * takes the pixel bounding box of those that land in the image.  Float64 as the reference:
+ * c = world_to_cam * [p, 1] (x, y, z only, each ((r0*x + r1*y) + r2*z) + t without FMA; the
+ * reference's BLAS order is its own), points with z > 0 strictly, u = fx * (x / z) + cx and
+ * v = fy * (y / z) + cy in three rounded operations each, rounded half to even, in bounds when
+ * 0 <= px < width and 0 <= py < height (tested on the rounded float: -0.5 is pixel 0, NaN, +-inf
+ * and anything int cannot hold are outside), box = (min px, min py, max px, max py) inclusive.
+ * DESIGN.md §2 (f6).  Drawing the box is not part of the library.
+ *
+ * mc_proj_boxes: points float64 [num_points, 3], or NULL for the mc_scene_set_points points
+ * widened exactly (MC_ERR_STATE unless num_points of them are set); the objects' point lists in CSR
+ * form (what mc_pp_export fills); intrinsics [num_frames, 4] = fx, fy, cx, cy; world_to_cam
+ * [num_frames, 16] row-major (the INVERSE of the reference's camera -> world extrinsics, computed
+ * by the caller); requests (req_object[i], req_frame[i]), duplicates allowed, order kept.
+ * on_device applies to every input array.  Out: boxes [n * 4], status [n] (MC_PROJ_OK,
+ * MC_PROJ_BEHIND: no point with z > 0, the reference returns None at :215-216; MC_PROJ_OUTSIDE: no
+ * point in the image, None at :228-229; the box of both is 0) and inside [n] (may be NULL): the
+ * number of in-bounds points, 0 without a box.  Host arrays or, with out_on_device, device
+ * pointers; then the call does not wait for its kernels (device INPUTS are checked by a kernel whose
+ * flag word the host reads first; host inputs are waited for, the uploads read the caller's arrays).  MC_ERR_INVALID, outputs untouched: an object or frame index
+ * out of range, offsets not rising from 0, a point id outside [0, num_points), width or height
+ * outside [1, 2^30], more than 2^20 requests.
+ *
+ * mc_proj_top_views: the same on the final objects of the context's last mc_pp_run* (MC_ERR_STATE
+ * without one), nothing crossing to the host in between: per final object the first top_k
+ * (1 .. 16; the reference draws 9) positions of its mask list by descending coverage, equal
+ * coverages in list order (value['mask_list'][:9] after find_represent_mask's in-place sort; the
+ * rule of obj_repre), each mask's frame column the request's frame.  points: the scene's float64
+ * points (the count mc_pp_run* saw) or NULL as above; num_frames at least the scene's.  Out, each
+ * [num_final * top_k] (boxes * 4), -1 where the object has fewer masks: top_pos (positions into the
+ * object's mask list of mc_pp_export), top_frame, boxes, status, inside (may be NULL).
+ * on_device: points, intrinsics, world_to_cam; out_on_device: the outputs. */
+#define MC_PROJ_OK 0
+#define MC_PROJ_BEHIND 1
+#define MC_PROJ_OUTSIDE 2
+int mc_proj_boxes(mc_ctx *ctx, int64_t num_points, const double *points, int32_t num_objects, const int64_t *obj_pt_off,
+                  const int32_t *obj_pts, int32_t num_frames, const double *intrinsics, const double *world_to_cam,
+                  int32_t width, int32_t height, int32_t num_requests, const int32_t *req_object, const int32_t *req_frame,
+                  int on_device, int32_t *boxes, int32_t *status, int32_t *inside, int out_on_device);
+int mc_proj_top_views(mc_ctx *ctx, const double *points, int32_t num_frames, const double *intrinsics,
+                      const double *world_to_cam, int32_t width, int32_t height, int on_device, int32_t top_k,
+                      int32_t *top_pos, int32_t *top_frame, int32_t *boxes, int32_t *status, int32_t *inside,
+                      int out_on_device);
+
 /* host utility: packed little-endian bit rows (bit c of word c/64 = column c) -> one byte per
  * column, rows * ncols bytes (the dense bool point_frame_matrix the reference's callers read,
  * graph/construction.py:40,52), split over host threads.                                      */

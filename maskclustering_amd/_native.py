@@ -45,6 +45,7 @@ EXPORTED = [
     "mc_ev_begin", "mc_ev_add_scan", "mc_ev_add_scan_clustered", "mc_ev_add_matches", "mc_ev_scan_info", "mc_ev_get_scan",
     "mc_ev_ap", "mc_ev_get_curve", "mc_ev_state_info", "mc_ev_state_export", "mc_ev_state_merge",
     "mc_crop_params_default", "mc_crop_boxes", "mc_crop_render", "mc_crop_coeffs",
+    "mc_proj_boxes", "mc_proj_top_views",
 ]
 MC_COMM_ID_BYTES = 128
 
@@ -225,6 +226,10 @@ def load():
         "mc_crop_render": (ctypes.c_int, [vp, i32, i32, i32, vp, ctypes.c_int, i32, vp, vp, vp, ctypes.c_int,
                                           P(CropParams), vp]),
         "mc_crop_coeffs": (ctypes.c_int, [vp, i32, i32, P(i32), vp, vp]),
+        "mc_proj_boxes": (ctypes.c_int, [vp, i64, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, ctypes.c_int, vp, vp,
+                                         vp, ctypes.c_int]),
+        "mc_proj_top_views": (ctypes.c_int, [vp, vp, i32, vp, vp, i32, i32, ctypes.c_int, i32, vp, vp, vp, vp, vp,
+                                             ctypes.c_int]),
     }
     # MCGRAPH_LIB_PARTIAL=1 (A/B scripts only): an older variant library may lack newer entry points
     partial = os.environ.get("MCGRAPH_LIB_PARTIAL") == "1"
@@ -1159,6 +1164,113 @@ def _crop_methods():
 
 
 _crop_methods()
+
+
+MC_PROJ_OK, MC_PROJ_BEHIND, MC_PROJ_OUTSIDE = 0, 1, 2
+
+
+def _proj_methods():
+    def _order(self):
+        """as the crops: wait for torch's current stream when the context runs on another one"""
+        import torch
+        cur = torch.cuda.current_stream(self.torch_device)
+        if (cur.cuda_stream or 0) == (self.stream() or 0):
+            return False
+        cur.synchronize()
+        return True
+
+    def _arrays(self, items, device):
+        """{name: (array, dtype name, shape)} -> (pointers, keep-alive): numpy arrays made contiguous, or
+        device tensors checked; None stays NULL"""
+        ptrs, keep = {}, []
+        for name, (a, dt, shape) in items.items():
+            if a is None:
+                ptrs[name] = None
+                continue
+            if device:
+                import torch
+                if not hasattr(a, "data_ptr") or a.device.type != "cuda" or a.dtype != getattr(torch, dt) or \
+                        not a.is_contiguous() or (shape is not None and tuple(a.shape) != tuple(shape)):
+                    raise ValueError(f"{name}: a contiguous {dt} device tensor of shape {shape}")
+                ptrs[name] = ctypes.c_void_p(a.data_ptr()) if a.numel() else None
+            else:
+                if hasattr(a, "detach"):
+                    a = a.detach().cpu().numpy()
+                a = np.ascontiguousarray(a, dt)
+                if shape is not None:
+                    a = a.reshape(shape)
+                ptrs[name] = _ptr(a)
+            keep.append(a)
+        return ptrs, keep
+
+    def _outputs(self, shapes, device):
+        if device:
+            import torch
+            out = {k: torch.full(sh, -1, dtype=torch.int32, device=self.torch_device) for k, sh in shapes.items()}
+            return out, {k: ctypes.c_void_p(v.data_ptr()) for k, v in out.items()}
+        out = {k: np.full(sh, -1, np.int32) for k, sh in shapes.items()}
+        return out, {k: _ptr(v) for k, v in out.items()}
+
+    def proj_boxes(self, points, obj_pt_off, obj_pts, intrinsics, world_to_cam, width, height, req_object, req_frame,
+                   device: bool = False, num_points: int | None = None):
+        """mc_proj_boxes: (boxes int32 [n, 4] = min px, min py, max px, max py; status int32 [n]; inside
+        int32 [n]) of the requests (req_object[i], req_frame[i]).  points float64 [P, 3] or None (the
+        num_points points of set_points), the objects' point lists in CSR form, intrinsics float64 [F, 4],
+        world_to_cam float64 [F, 4, 4].  All numpy, or all tensors on the context's device; device=True:
+        the outputs are device tensors, otherwise numpy arrays."""
+        on_dev = hasattr(obj_pt_off, "data_ptr") and obj_pt_off.device.type == "cuda"
+        F = int(intrinsics.shape[0])
+        n = int(req_object.shape[0]) if hasattr(req_object, "shape") else len(req_object)
+        if points is None and num_points is None:
+            raise ValueError("proj_boxes: num_points is needed without points")
+        P = int(num_points) if points is None else int(points.shape[0])
+        if not on_dev:
+            clip = lambda a: np.clip(np.asarray(a, np.int64).reshape(-1), -1, 2 ** 31 - 1)  # noqa: E731
+            req_object, req_frame = clip(req_object), clip(req_frame)
+        p, keep = _arrays(self, dict(points=(points, "float64", (P, 3)), off=(obj_pt_off, "int64", None),
+                                     pts=(obj_pts, "int32", None), intr=(intrinsics, "float64", (F, 4)),
+                                     w2c=(world_to_cam, "float64", (F, 4, 4)), robj=(req_object, "int32", (n,)),
+                                     rframe=(req_frame, "int32", (n,))), on_dev)
+        K = int(obj_pt_off.shape[0]) - 1
+        out, op = _outputs(self, dict(boxes=(n, 4), status=(n,), inside=(n,)), device)
+        settle = _order(self) if (on_dev or device) else False
+        if not n:
+            op = dict(boxes=None, status=None, inside=None)
+        self._check(self.L.mc_proj_boxes(self.h, P, p["points"], K, p["off"], p["pts"], F,
+                                         p["intr"], p["w2c"], int(width), int(height), n, p["robj"], p["rframe"],
+                                         1 if on_dev else 0, op["boxes"], op["status"], op["inside"], 1 if device else 0))
+        if settle and device:
+            self.synchronize()
+        return out["boxes"], out["status"], out["inside"]
+
+    def proj_top_views(self, intrinsics, world_to_cam, width, height, top_k: int = 9, points=None, device: bool = False):
+        """mc_proj_top_views on the last pp_run* result: dict of top_pos, top_frame, status, inside int32
+        [num_final, top_k] and boxes int32 [num_final, top_k, 4], -1 where an object has fewer masks.
+        intrinsics float64 [F, 4] and world_to_cam float64 [F, 4, 4] (and points float64 [P, 3], None:
+        the points of set_points): all numpy, or all tensors on the context's device.  device=True:
+        device tensors, and with the context on torch's current stream nothing waits."""
+        on_dev = hasattr(intrinsics, "data_ptr") and intrinsics.device.type == "cuda"
+        F = int(intrinsics.shape[0])
+        p, keep = _arrays(self, dict(points=(points, "float64", None), intr=(intrinsics, "float64", (F, 4)),
+                                     w2c=(world_to_cam, "float64", (F, 4, 4))), on_dev)
+        k = int(top_k)
+        nf = self.pp_export_sizes()[0]
+        kk = k if 1 <= k <= 16 else 0    # an invalid top_k is the library's to refuse: no output is sized by it
+        out, op = _outputs(self, dict(top_pos=(nf, kk), top_frame=(nf, kk), boxes=(nf, kk, 4), status=(nf, kk),
+                                      inside=(nf, kk)), device)
+        settle = _order(self) if (on_dev or device) else False
+        self._check(self.L.mc_proj_top_views(self.h, p["points"], F, p["intr"], p["w2c"], int(width), int(height),
+                                             1 if on_dev else 0, k, op["top_pos"], op["top_frame"], op["boxes"],
+                                             op["status"], op["inside"], 1 if device else 0))
+        if settle and device:
+            self.synchronize()
+        return out
+
+    for f in (proj_boxes, proj_top_views):
+        setattr(Context, f.__name__, f)
+
+
+_proj_methods()
 
 
 def bits_unpack(words, ncols):

@@ -19,6 +19,7 @@
 #include "mc_graph_plan.hpp"
 #include "mc_pp_plan.hpp"
 #include "mc_crop_plan.hpp"
+#include "mc_proj_plan.hpp"
 #include "mc_kernels.inl"
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
@@ -28,6 +29,7 @@
 #include "mc_shard_kernels.inl"
 #include "mc_ov_kernels.inl"
 #include "mc_crop_kernels.inl"
+#include "mc_proj_kernels.inl"
 #include "mc_setorder.inl"
 
 using mc::DevBuf;
@@ -162,6 +164,15 @@ struct CropState {
     std::vector<float> h_lut;
 };
 
+// projected boxes (mc_proj_*; the host code is mc_proj_host.inl): the context's pools
+struct ProjState {
+    DevBuf pts, intr, w2c, opoff, opts;          // host arguments' device copies (pts also: the widened scene points)
+    DevBuf gobj, goff, rframe, rout;             // the request groups of mc_proj_boxes
+    DevBuf acc, flag, ocol;                      // accumulators, the check flag, the final objects' mask frames
+    DevBuf out_pos, out_frame, out_boxes, out_status, out_inside;  // host outputs' device copies
+    std::vector<int32_t> h_gobj, h_goff, h_rframe, h_rout;         // staged until the next call
+};
+
 }  // namespace
 
 struct mc_ctx {
@@ -244,7 +255,9 @@ struct mc_ctx {
     std::vector<uint8_t> pp_state;
     // the node arrays and per-entry results of the last run, resident for the export
     DevBuf d_pp_npoff, d_pp_npts, d_pp_qoff, d_pp_qm, d_pp_eobj, d_pp_qobj, d_pp_qcov;
+    DevBuf d_pp_qcol;  // the node masks' frame columns (mc_proj_top_views)
     int64_t pp_P = 0;
+    int pp_F = 0;
     bool pp_host = false;    // pp_entry_obj / pp_qobj / pp_qcov are fetched (mc_pp_get_results)
     bool pp_export = false;  // the export arrays below are built
     std::vector<int32_t> pp_fslot, pp_fin, pp_fin_node;  // object -> final slot; final objects, their nodes
@@ -253,6 +266,7 @@ struct mc_ctx {
 
     EvState ev;  // AP evaluation (mc_ev_*)
     CropState crop;  // CLIP crop preparation (mc_crop_*)
+    ProjState proj;  // projected boxes (mc_proj_*)
 };
 
 namespace {
@@ -472,6 +486,7 @@ int mc_debug_counters(mc_ctx *ctx, int64_t *out, int32_t n, int reset)
 #include "mc_bp_host.inl"
 #include "mc_pp_host.inl"
 #include "mc_crop_host.inl"
+#include "mc_proj_host.inl"
 
 extern "C" {
 

@@ -246,6 +246,7 @@ void pp_publish(mc_ctx *ctx, PPRun &r, const std::vector<int32_t> &base, const m
     ctx->d_pp_qobj.swap(r.qobj);
     ctx->d_pp_qcov.swap(r.qcov);
     ctx->pp_P = r.a.P;
+    ctx->pp_F = r.a.F;
     ctx->pp_host = ctx->pp_export = false;
     if (host_results) pp_fetch_host(ctx);
     else {
@@ -427,6 +428,7 @@ int mc_pp_run(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points, int32
         a.mask_pts = mpts.as<int>(), a.npts = ctx->d_pp_npts.as<int>(), a.qm = ctx->d_pp_qm.as<int>();
         a.qcol = qcol.as<int>();
         pp_run(ctx, r, true);
+        ctx->d_pp_qcol.swap(qcol);
     });
 }
 
@@ -452,8 +454,10 @@ int mc_pp_run_device(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points
         pp_upload(s, ctx->d_pp_npts, a.npts, static_cast<size_t>(a.E) * 4, hipMemcpyDeviceToDevice);
         pp_upload(s, ctx->d_pp_qoff, a.qoff, static_cast<size_t>(a.N + 1) * 8, hipMemcpyDeviceToDevice);
         pp_upload(s, ctx->d_pp_qm, a.qm, static_cast<size_t>(a.Q) * 4, hipMemcpyDeviceToDevice);
+        pp_upload(s, ctx->d_pp_qcol, a.qcol, static_cast<size_t>(a.Q) * 4, hipMemcpyDeviceToDevice);
         a.npoff = ctx->d_pp_npoff.as<int64_t>(), a.npts = ctx->d_pp_npts.as<int>();
         a.qoff = ctx->d_pp_qoff.as<int64_t>(), a.qm = ctx->d_pp_qm.as<int>();
+        a.qcol = ctx->d_pp_qcol.as<int>();
         pp_run(ctx, r, false);
     });
 }
@@ -551,6 +555,7 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
         a.qcol = qcol.as<int>();
         pp_check_args(ctx, params, r, false);
         pp_run(ctx, r, false);
+        ctx->d_pp_qcol.swap(qcol);
     });
 }
 

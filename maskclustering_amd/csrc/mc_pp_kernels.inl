@@ -923,8 +923,47 @@ __global__ __launch_bounds__(256) void k_pp_ex_fill(int nfin, const int *__restr
     }
 }
 
+// The order of find_represent_mask's sort (:126-128), by one wave: the positions of the k largest of
+// the n coverages cov[0 .. n), equal coverages in list order (Python's sort is stable), INT_MAX
+// past the end.  emit(rank, position) runs in every lane with the same arguments.
+template <typename Emit>
+__device__ __forceinline__ void pp_cov_top(const double *__restrict__ cov, int n, int k, int lane, Emit &&emit)
+{
+    double pc = 0.0;  // the pick before this one
+    int pp = -1;
+    for (int r = 0; r < k; r++) {
+        double bc = 0.0;
+        int bp = INT_MAX;
+        for (int i = lane; i < n; i += 64) {
+            const double c = cov[i];
+            const bool after = pp < 0 || c < pc || (c == pc && i > pp);
+            if (after && (bp == INT_MAX || c > bc)) {
+                bc = c;
+                bp = i;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const double oc = __shfl_xor(bc, d, 64);
+            const int op = __shfl_xor(bp, d, 64);
+            if (op != INT_MAX && (bp == INT_MAX || oc > bc || (oc == bc && op < bp))) {
+                bc = oc;
+                bp = op;
+            }
+        }
+        emit(r, bp);
+        if (bp == INT_MAX) {  // (uniform) nothing left
+            pp = n;
+            pc = -1.0;
+        } else {
+            pc = bc;
+            pp = bp;
+        }
+    }
+}
+
 // find_represent_mask (:126-128): positions of the five largest coverages in an object's mask list,
-// equal coverages in list order (Python's sort is stable), -1 past the end; a wave per object
+// -1 past the end; a wave per object
 __global__ __launch_bounds__(256) void k_pp_ex_repre(int nfin, const int64_t *__restrict__ omoff,
                                                      const double *__restrict__ ocov, int *__restrict__ repre)
 {
@@ -932,37 +971,9 @@ __global__ __launch_bounds__(256) void k_pp_ex_repre(int nfin, const int64_t *__
     for (int f = blockIdx.x * 4 + (threadIdx.x >> 6); f < nfin; f += gridDim.x * 4) {
         const int64_t a = omoff[f];
         const int n = static_cast<int>(omoff[f + 1] - a);
-        double pc = 0.0;  // the pick before this one
-        int pp = -1;
-        for (int r = 0; r < 5; r++) {
-            double bc = 0.0;
-            int bp = INT_MAX;
-            for (int i = lane; i < n; i += 64) {
-                const double c = ocov[a + i];
-                const bool after = pp < 0 || c < pc || (c == pc && i > pp);
-                if (after && (bp == INT_MAX || c > bc)) {
-                    bc = c;
-                    bp = i;
-                }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const double oc = __shfl_xor(bc, d, 64);
-                const int op = __shfl_xor(bp, d, 64);
-                if (op != INT_MAX && (bp == INT_MAX || oc > bc || (oc == bc && op < bp))) {
-                    bc = oc;
-                    bp = op;
-                }
-            }
+        pp_cov_top(ocov + a, n, 5, lane, [&](int r, int bp) {
             if (lane == 0) repre[5 * f + r] = bp == INT_MAX ? -1 : bp;
-            if (bp == INT_MAX) {  // (uniform) nothing left
-                pp = n;
-                pc = -1.0;
-            } else {
-                pc = bc;
-                pp = bp;
-            }
-        }
+        });
     }
 }
 

@@ -193,6 +193,20 @@ class SceneSweep:
         ``run.mask_label``) with coverages, representative masks and source nodes."""
         return self.ctx.pp_export(device=device)
 
+    def top_views(self, intrinsics, poses, width, height, top_k: int = 9, device: bool = False) -> dict:
+        """Which frames show each final object best, and where in them (the geometry of the reference's
+        ``get_top_images.py``; ``Context.proj_top_views``), after ``run_scene(..., post_process=...)``.
+        intrinsics [F,4] and poses [F,16] camera -> world as ``run_scene`` takes them (device tensors
+        or numpy); width, height: the image size the boxes are clipped to (the reference takes it from
+        the intrinsics object, not from the frames).  The poses are inverted with numpy on the host,
+        as the reference inverts them.  Returns ``top_pos`` (positions into the object's mask list of
+        ``objects()``), ``top_frame``, ``status``, ``inside`` [num_final, top_k] and ``boxes``
+        [num_final, top_k, 4], -1 where an object has fewer masks: numpy, or device tensors."""
+        from ._device import as_numpy
+        k = np.ascontiguousarray(as_numpy(intrinsics), np.float64).reshape(-1, 4)
+        w2c = np.linalg.inv(np.asarray(as_numpy(poses), np.float64).reshape(-1, 4, 4))
+        return self.ctx.proj_top_views(k, w2c, width, height, top_k=top_k, device=device)
+
     def pred_masks(self, device: bool = False):
         """The [P, num_final] uint8 matrix of the reference's prediction npz."""
         return self.ctx.pp_pred_masks(self.run.P, device=device)
