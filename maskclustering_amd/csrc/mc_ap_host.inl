@@ -563,12 +563,13 @@ int mc_ev_add_scan(mc_ctx *ctx, int64_t num_points, const int32_t *gt_ids, int32
 int mc_ev_add_scan_clustered(mc_ctx *ctx, const int32_t *gt_ids, int on_device)
 {
     return guarded(ctx, [&] {
+        PpState &pp = ctx->pp;
         EvState &ev = ctx->ev;
         MC_REQUIRE(ev.active, MC_ERR_STATE, "mc_ev_begin first");
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
+        MC_REQUIRE(pp.have, MC_ERR_STATE, "no post-processing result");
         pp_build_export(ctx);
-        const int nf = ctx->pp_info.num_final;
-        const int64_t P = ctx->pp_P, np = ctx->pp_opoff[nf];
+        const int nf = pp.info.num_final;
+        const int64_t P = pp.P, np = pp.opoff[nf];
         MC_REQUIRE(P == 0 || gt_ids, MC_ERR_INVALID, "null argument");
         MC_REQUIRE(P < INT32_MAX && np < INT32_MAX, MC_ERR_UNSUPPORTED, "scene too large");
         const int *gt = gt_ids;
@@ -577,7 +578,7 @@ int mc_ev_add_scan_clustered(mc_ctx *ctx, const int32_t *gt_ids, int on_device)
             if (P) MC_HIP(hipMemcpyAsync(ev.d_in[0].ptr, gt_ids, static_cast<size_t>(P) * 4, hipMemcpyHostToDevice, ctx->stream));
             gt = ev.d_in[0].as<int>();
         }
-        ev_scan_device(ctx, P, gt, nf, ctx->d_pp_opoff.as<int64_t>(), np, ctx->d_pp_opts.as<int>(), nullptr, nullptr);
+        ev_scan_device(ctx, P, gt, nf, pp.d_opoff.as<int64_t>(), np, pp.d_opts.as<int>(), nullptr, nullptr);
     });
 }
 

@@ -35,6 +35,7 @@ constexpr int kEvMaxOverlaps = 32;  // one bit per overlap in k_ev_qual's masks
 constexpr int kEvCountLds = 8192;   // ids k_ev_gt_count_lds counts in LDS
 
 // exclusive scan of one int per thread over the workgroup (blockDim.x a multiple of 64, <= 1024)
+// (restates block_excl_scan of mc_dev_common.inl for a block size known only at run time)
 __device__ inline int ev_block_scan(int v, int *wsum /* LDS [17] */, int &total)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;

@@ -1,6 +1,9 @@
-// mc_api.hip — C-ABI of libmcgraph: the context, the error guard, the small stateless entries.
-// Single translation unit: the kernels live in mc_*kernels.inl, the host drivers in mc_*_host.inl
-// (included below), the decisions they take between kernels in mc_*_plan.hpp.
+// mc_api.hip — C-ABI of libmcgraph, the single translation unit: the includes, the error guard and the
+// helpers every driver uses (fail, guarded, grid_for, sync_stats, fetch), the context's lifecycle and timing
+// entries (mc_ctx_*), the host-driver includes, and the four small stateless entries.  The context and its
+// state structs are mc_ctx.hpp, the kernels live in mc_*kernels.inl (mc_kernels.inl and mc_bp_kernels.inl
+// are umbrellas of one file per stage), the host drivers in mc_*_host.inl, the decisions they take between
+// kernels in mc_*_plan.hpp.
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types only: the library loads RCCL at mc_ctx_attach_comm / mc_ctx_comm_init (dlopen)
 
@@ -37,28 +40,9 @@ using mc::McError;
 using mc::TimedScope;
 using mc::ceil_div;
 
+#include "mc_ctx.hpp"
+
 namespace {
-
-// device-side statistics block (copied to pinned host memory in one transfer)
-enum Stat : int {
-    ST_NBND = 0,      // boundary points
-    ST_NNZC = 1,      // contained entries after undo
-    ST_N0 = 2,        // level-0 nodes
-    ST_NTHR = 3,      // thresholds
-    ST_THR_STATUS = 4,
-    ST_K = 5,         // final objects
-    ST_WORDS = 6,     // point-bitmap words
-    ST_NPTS = 7,      // object points (sum)
-    ST_OBJOVF = 8,    // a point in more objects than the per-point fast path holds
-    ST_COUNT = 9,
-};
-
-// the arrays of one S6 level (device pointers): per node the offset and length of its row of
-// contained masks in `pool`, the owner node of every pool entry, the nodes' visible-frame words
-struct S6Level {
-    int *off = nullptr, *len = nullptr, *pool = nullptr, *own = nullptr;
-    unsigned long long *vf = nullptr;
-};
 
 // MC_STAGE_THREADS: host threads of the staging copies (mc_backproject_frames, mc_bits_unpack)
 int stage_threads_knob(int dflt)
@@ -66,210 +50,6 @@ int stage_threads_knob(int dflt)
     if (const char *e = getenv("MC_STAGE_THREADS")) return std::max(1, std::min(64, atoi(e)));
     return dflt;
 }
-
-// S1 back-projection state of a context (the host code is mc_bp_host.inl)
-struct BpState {
-    // scene points and their 2r grid
-    int64_t P = 0;
-    bool have_points = false, have_result = false;
-    float grid_radius = -1.f;  // scene grid built for this ball radius
-    unsigned gnb = 0;
-    DevBuf scene, gcnt, gstart, gbkt, gcellk, gpts, gidx, gcell, gscan_tmp;
-    // frames that arrive from the host
-    DevBuf in_depth, in_seg, in_intr, in_pose, in_raw;
-    char *h_stage[2] = {nullptr, nullptr};  // pinned staging ring of mc_backproject_frames (two chunks, ping-pong)
-    size_t stage_bytes = 0;
-    hipEvent_t ev_stage[2] = {};
-    bool stage_used[2] = {false, false};
-    hipStream_t copy = nullptr;  // host frames staged batch by batch while the previous batch computes
-    hipEvent_t ev_up = nullptr;
-    // per-batch arrays
-    DevBuf band, present, fflags, cand, npix, csidx, poff, slot_of, stat;
-    DevBuf vid;  // valid-id map (k_bp_count -> k_bp_compact), 1 byte per pixel
-    DevBuf slot_frame, slot_id, slot_np, slot_pix, slot_nv, slot_m, slot_ns, slot_box, slot_nn, slot_toff, slot_cov;
-    DevBuf pix_list, hkey, hvid, hfirst, vox_entry, acc, vpts, pcell, pbkt, bcnt, bstart, blist, ncnt, par, droot, rnk,
-        lab, ccnt, ssidx, avg, qpts;
-    DevBuf bm, tmp, kflag, ksize, midx, moff, out_col, out_label, out_off;
-    DevBuf cls_list, nbl, lean, vox_order;  // denoise size-class slot lists; per-workgroup eps-neighbour lists, lean scratch
-    DevBuf vx_pvid, vx_list, vx_fb;  // voxel_down_sample: per-pixel voxel ids and voxel lists of k_bp_voxel_lds; its overflow slots
-    DevBuf q_fb;       // ball query: the slots k_bp_query_lds hands to k_bp_query
-    DevBuf scanm;      // block sums of the multi-workgroup scans
-    DevBuf slot_grid;  // denoise: grid origin / extent of the slots with points queued for the k-NN ring search
-    DevBuf pack;       // the batch's readback, packed (k_bp_pack)
-    int *h_pack = nullptr;  // its pinned copy, h_pack_n ints
-    size_t h_pack_n = 0;
-    hipEvent_t ev_pack = nullptr;  // the last batch's h_pack copy (appended under the next batch)
-    int *h_stat = nullptr;         // pinned copy of the status block
-    hipStream_t cls_stream[mc::kBpStreamClasses] = {};  // denoise: the LDS size classes run side by side
-    hipEvent_t ev_cls[mc::kBpStreamClasses] = {};
-    // batch sizing
-    int64_t mem_budget = 0;  // bytes the per-batch arrays may take (0: the default share, mc_bp_plan.hpp)
-    size_t px_cap = 0;       // mask-pixel capacity of the per-batch arrays (pixel-list positions)
-    size_t fpx_cap = 0;      // frame-pixel capacity (the valid-id map)
-    double mfrac = 1.0;      // mask pixels per frame pixel a batch is sized for (the largest seen, + margin)
-    bool mfrac_obs = false;  // mfrac comes from an earlier call's batches (not the initial guess)
-    int last_fb = 0;         // frames per batch at the end of the last call
-    int64_t redo = 0;        // batches redone after a mask-pixel overflow (all calls)
-    // results of the last call
-    int F = 0, err_frame = -1;
-    int64_t nnz = 0;
-    DevBuf pts;  // the masks' point lists
-    std::vector<int32_t> col, label, stats;
-    std::vector<int64_t> off;
-};
-
-// AP evaluation state of a context (the host code is mc_ap_host.inl)
-struct EvTables {  // one scan's compact tables (include/mcgraph.h, mc_ev_get_scan)
-    std::vector<int32_t> gcls, gid, pcls, ppred, pgt;
-    std::vector<int64_t> gvert, pvert, pvoid, pint;
-    std::vector<double> pscore;
-};
-
-struct EvState {
-    bool active = false;
-    int C = 0, O = 0, nlab = 0;
-    int64_t min_region = 100;
-    bool no_class = false;
-    std::vector<int32_t> class_ids;
-    std::vector<double> overlaps;
-    DevBuf d_lab2cls, d_overlaps;
-    // accumulated over the scans: examples in per-unit regions, one unit per (scan, class, overlap)
-    int64_t ex_used = 0;
-    int units = 0;
-    DevBuf d_ex_key, d_ex_true, d_unit_cell, d_unit_off, d_unit_cnt, d_hardfn, d_flags;
-    EvTables last;
-    bool have_last = false;
-    // the table of the last mc_ev_ap
-    bool ap_valid = false;
-    std::vector<double> ap;
-    std::vector<int64_t> stats;
-    std::vector<int32_t> ndist;
-    DevBuf d_key, d_true, d_prec, d_rec, d_cell, d_ap, d_stats, d_ndist;
-    // the accumulation as runs (mc_ev_state_*): the state buffer of the last export, kept on the device
-    bool runs_valid = false;
-    int64_t state_runs = 0, state_examples = 0, state_bytes = 0;
-    DevBuf d_state, d_run, d_merge;
-    // scratch of one mc_ev_add_scan / commit
-    std::vector<int64_t> h_out;
-    DevBuf d_info, d_in[5], d_cnt, d_inst, d_tmp_id, d_class, d_gcls, d_gid, d_gvert, d_pinst, d_pk, d_pair_gt, d_pair_int,
-        d_out, d_words, d_tmp;
-};
-
-// CLIP crop preparation (mc_crop_*; the host code is mc_crop_host.inl): the context's pools
-struct CropState {
-    DevBuf tab, frames, slot, label;          // boxes: per-frame label tables, the referenced frames, per-mask slot / label
-    DevBuf in_seg, in_rgb, in_boxes, in_status, out_boxes, out_status;  // host arguments' device copies
-    DevBuf mframe, lut, bounds, kk, tmp;      // render: per-mask frame, 3 x 256 table, coefficient tables, intermediate
-    std::vector<int32_t> h_frames, h_slot, h_label, h_mframe;  // staged until the next call
-    std::vector<float> h_lut;
-};
-
-// projected boxes (mc_proj_*; the host code is mc_proj_host.inl): the context's pools
-struct ProjState {
-    DevBuf pts, intr, w2c, opoff, opts;          // host arguments' device copies (pts also: the widened scene points)
-    DevBuf gobj, goff, rframe, rout;             // the request groups of mc_proj_boxes
-    DevBuf acc, flag, ocol;                      // accumulators, the check flag, the final objects' mask frames
-    DevBuf out_pos, out_frame, out_boxes, out_status, out_inside;  // host outputs' device copies
-    std::vector<int32_t> h_gobj, h_goff, h_rframe, h_rout;         // staged until the next call
-};
-
-}  // namespace
-
-struct mc_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipStream_t side = nullptr;                 // S3: workgroup-per-mask kernel beside the wave kernel
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    std::string err;
-    mc::KernelTimer timer;
-    int *h_stats = nullptr;  // pinned
-    int num_cu = 256;
-    BpState bp;  // S1 back-projection
-
-    // ---- scene ----
-    bool have_scene = false, have_graph = false, have_nodes = false, have_cluster = false;
-    bool nodes_from_graph = false;
-    int64_t P = 0;
-    int F = 0, FW = 0, M = 0, M_in = 0;
-    int nnz = 0;
-    std::vector<int32_t> h_col, h_label, h_in_index, h_off;
-    DevBuf d_mask_off, d_mask_pts, d_mask_col, d_mask_label, d_frame_start, d_valid;
-    // ---- S2 ----
-    DevBuf d_deg, d_pt_off, d_pt_list, d_boundary, d_pfm, d_scan_tmp;
-    // ---- S3/S5 ----
-    DevBuf d_ctmp, d_crow_len, d_useg, d_keep_cnt, d_node_flag, d_node_pos, d_c_off, d_c_idx, d_vf;
-    // ---- S4 ----
-    DevBuf d_hist, d_thr, d_isint, d_stats, d_s4rng;
-    // ---- level-0 nodes ----
-    int N0 = 0;        // host copy (valid after sync_stats or mc_nodes_set)
-    int Mn = 0;        // mask-id space of C rows
-    int64_t n0_pts_total = 0;
-    DevBuf d_node0_g, d_n0_off, d_n0_len, d_n0_ptoff, d_n0_ptlen, d_n0_vf, d_user_cidx, d_user_pts;
-    DevBuf d_owner0, d_node_of_mask, d_obj_of_mask, d_s3_small, d_s3_big, d_collen;
-    int n_s3_small = 0, n_s3_big = 0;
-    int *n0_pool = nullptr;
-    const int *n0_pts = nullptr;
-    int64_t nnzC0 = 0;
-    // ---- S6 ----
-    DevBuf d_parent, d_root, d_isroot, d_rank, d_label, d_levels, d_memcnt, d_memoff, d_ublen, d_newoff;
-    DevBuf d_members, d_colcnt, d_coloff, d_colnodes, d_ovf_n, d_scratch, d_touched, d_edges;
-    DevBuf d_spread;  // spread slots of the S2 boundary counter
-    DevBuf d_Nlev, d_final_label;
-    DevBuf d_poolA, d_poolB, d_offA, d_offB, d_lenA, d_lenB, d_vfA, d_vfB, d_ownA, d_ownB, d_cap;
-    DevBuf d_pmin, d_pmax, d_nwords, d_woff, d_bm, d_ptcnt, d_ptoff_out, d_pts_out;
-    int scratch_n0 = -1;
-    int n_iter = 0;
-    S6Level fin;  // the final objects (the last level, in the pools)
-    int K = 0;
-    int64_t npts = 0;
-
-    // ---- row-block sharding over processes ----
-    int sh_rank = 0, sh_world = 1;
-    int sh_pending = 0;          // MC_SHARD_* phase waiting for the host's exchange, 0 = none
-    int sh_r0 = 0, sh_r1 = 0;    // this rank's S3 mask rows
-    int64_t sh_s3_words = -1;    // size of this rank's S3 block (valid while sh_pending == MC_SHARD_S3)
-    mc_graph_params sh_params{};
-    DevBuf d_sh_eoff;
-    // native collectives (mc_ctx_attach_comm / mc_ctx_comm_init): with a communicator attached the
-    // sharded mc_graph_build / mc_cluster_run run their exchanges themselves, on the context stream
-    void *comm = nullptr;        // ncclComm_t
-    bool own_comm = false;
-    DevBuf d_sh_send, d_sh_recv, d_sh_size;
-    // S6 state kept across the FOREST exchange
-    int s6_nthr = 0;
-    bool s6_dense_obs = false;
-    float s6_ctf = 0.f;
-    // edge capture for the set-order replay (mc_cluster_set_edge_capture)
-    int64_t cap_edges = 0;
-    DevBuf d_cap_buf, d_cap_cnt;
-
-    // ---- post-processing ----
-    DevBuf d_pp_posmap;  // one P-entry position map per workgroup, -1 at rest
-    int64_t pp_posmap_P = 0;
-    int pp_posmap_slots = 0;
-    bool have_pp = false;
-    mc_pp_info pp_info{};
-    std::vector<int32_t> pp_entry_obj, pp_qobj, pp_obj_node;
-    std::vector<double> pp_qcov, pp_box;
-    std::vector<uint8_t> pp_state;
-    // the node arrays and per-entry results of the last run, resident for the export
-    DevBuf d_pp_npoff, d_pp_npts, d_pp_qoff, d_pp_qm, d_pp_eobj, d_pp_qobj, d_pp_qcov;
-    DevBuf d_pp_qcol;  // the node masks' frame columns (mc_proj_top_views)
-    int64_t pp_P = 0;
-    int pp_F = 0;
-    bool pp_host = false;    // pp_entry_obj / pp_qobj / pp_qcov are fetched (mc_pp_get_results)
-    bool pp_export = false;  // the export arrays below are built
-    std::vector<int32_t> pp_fslot, pp_fin, pp_fin_node;  // object -> final slot; final objects, their nodes
-    std::vector<int64_t> pp_opoff, pp_omoff;             // point / mask list offsets of the final objects
-    DevBuf d_pp_fslot, d_pp_finobj, d_pp_finnode, d_pp_opoff, d_pp_omoff, d_pp_opts, d_pp_omask, d_pp_ocov, d_pp_repre;
-
-    EvState ev;  // AP evaluation (mc_ev_*)
-    CropState crop;  // CLIP crop preparation (mc_crop_*)
-    ProjState proj;  // projected boxes (mc_proj_*)
-};
-
-namespace {
 
 int fail(mc_ctx *ctx, const McError &e)
 {
@@ -358,7 +138,7 @@ void mc_ctx_destroy(mc_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->comm) {
+    if (ctx->shard.comm) {
         try {
             comm_detach(ctx);
         } catch (const McError &) {

@@ -112,6 +112,7 @@ __device__ __forceinline__ double wave_max_d(double v)
 }
 
 // block (256) min / max of 3 doubles, broadcast to every thread; red holds 2*3*4 doubles
+// (pp_block_minmax3, mc_pp_kernels.inl, restates it for NT threads)
 __device__ __forceinline__ void block_minmax3(double mn[3], double mx[3], double *red)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -49,6 +49,7 @@ __device__ __forceinline__ void bp_shell(const BpCells &g, int cx, int cy, int c
 }
 
 // union-find over a workgroup's LDS parent array (root = smallest index)
+// (uf_find_s / uf_unite_s restate uf_find / uf_unite of mc_s6_columns.inl at workgroup scope)
 constexpr int kBpLdsUF = 8192;
 // (relaxed workgroup-scope atomic loads / stores: other lanes update the array concurrently, and
 // unlike volatile they keep the LDS address space, i.e. ds_read / ds_write instead of flat ops)

@@ -1,6 +1,7 @@
 // mc_bp_kernels.inl — S1 mask back-projection for gfx950 (utils/mask_backprojection.py:70-151 with
-// utils/geometry.py:9-24); included by mc_api.hip after mc_kernels.inl.  The kernels live in one file
-// per step of bp_run (the includes below); this file holds what they all see.
+// utils/geometry.py:9-24); included by mc_api.hip after mc_kernels.inl, whose mc_dev_common.inl
+// (wave and block helpers, sync_global) and mc_scan.inl (the device scans) these kernels use.  The kernels
+// live in one file per step of bp_run (the includes below); this file holds what they all see.
 //
 // The Open3D / pytorch3d semantics restated here are those of oracle/s1_oracle.c, whose header lists
 // the choices (u1)-(u4) made where the libraries' result is not determined by their algorithm.  The

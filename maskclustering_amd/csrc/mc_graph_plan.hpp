@@ -1,8 +1,8 @@
 // mc_graph_plan.hpp — graph build and clustering: the decisions the host takes around the kernels.
 // Pure host arithmetic (no HIP include, plain C++17), used by mc_graph_host.inl, mc_cluster_host.inl
 // and mc_shard_host.inl and checked on the CPU by tests/test_graph_plan_cpu.py
-// (scripts/graph_plan_check.cpp).  The kernels' constants come in as arguments (mc_kernels.inl
-// defines them).  The rules:
+// (scripts/graph_plan_check.cpp).  The kernels' constants come in as arguments (each is defined
+// beside its kernel: the S3 limits in mc_s3_kernels.inl; mc_kernels.inl's table says where).  The rules:
 //  * Frame starts: the kept masks are in frame order; fs[c] is the first mask of a frame >= c.
 //  * Shard row cut: the mask rows go to the ranks in contiguous blocks of about equal point counts;
 //    rank k starts at the first row at which the cumulative points reach ceil(tot * k / W).

@@ -34,22 +34,23 @@ struct PPRun {
 // entry_object / mask_object / mask_coverage on the host (mc_pp_get_results)
 void pp_fetch_host(mc_ctx *ctx)
 {
-    if (ctx->pp_host) return;
+    PpState &pp = ctx->pp;
+    if (pp.host) return;
     hipStream_t s = ctx->stream;
-    const int64_t E = ctx->pp_info.num_entries, Q = ctx->pp_info.num_node_masks;
-    ctx->pp_entry_obj.resize(E);
-    ctx->pp_qobj.resize(Q);
-    ctx->pp_qcov.resize(Q);
-    if (E) MC_HIP(hipMemcpyAsync(ctx->pp_entry_obj.data(), ctx->d_pp_eobj.ptr, E * 4, hipMemcpyDeviceToHost, s));
+    const int64_t E = pp.info.num_entries, Q = pp.info.num_node_masks;
+    pp.entry_obj.resize(E);
+    pp.qobj.resize(Q);
+    pp.qcov.resize(Q);
+    if (E) MC_HIP(hipMemcpyAsync(pp.entry_obj.data(), pp.d_eobj.ptr, E * 4, hipMemcpyDeviceToHost, s));
     if (Q) {
-        MC_HIP(hipMemcpyAsync(ctx->pp_qobj.data(), ctx->d_pp_qobj.ptr, Q * 4, hipMemcpyDeviceToHost, s));
-        MC_HIP(hipMemcpyAsync(ctx->pp_qcov.data(), ctx->d_pp_qcov.ptr, Q * 8, hipMemcpyDeviceToHost, s));
+        MC_HIP(hipMemcpyAsync(pp.qobj.data(), pp.d_qobj.ptr, Q * 4, hipMemcpyDeviceToHost, s));
+        MC_HIP(hipMemcpyAsync(pp.qcov.data(), pp.d_qcov.ptr, Q * 8, hipMemcpyDeviceToHost, s));
     }
     MC_HIP(hipStreamSynchronize(s));
     ctx->timer.collect();
-    for (auto &o : ctx->pp_entry_obj)
-        if (o >= 0 && ctx->pp_state[o] != 2) o = -1;
-    ctx->pp_host = true;
+    for (auto &o : pp.entry_obj)
+        if (o >= 0 && pp.state[o] != 2) o = -1;
+    pp.host = true;
 }
 
 // dbscan_process: the nodes above big_min points (the first nbig of the size order) split over the chip,
@@ -119,17 +120,18 @@ std::vector<int32_t> pp_dbscan(mc_ctx *ctx, PPRun &r)
 // filter_point of the K objects; the per-object counts and boxes come to the host
 void pp_filter(mc_ctx *ctx, PPRun &r, int K)
 {
+    PpState &pp = ctx->pp;
     hipStream_t s = ctx->stream;
     const mc::PPArgs &a = r.a;
     const int N = a.N;
     const int64_t P = a.P, E = a.E, Q = a.Q, H = r.H;
     const int slots = std::max(1, std::min(N, ctx->num_cu));
-    if (ctx->pp_posmap_P < P || ctx->pp_posmap_slots < slots) {
-        ctx->d_pp_posmap.release();
-        ctx->d_pp_posmap.reserve(static_cast<size_t>(slots) * P * 4 + 8);
-        MC_HIP(hipMemsetAsync(ctx->d_pp_posmap.ptr, 0xFF, static_cast<size_t>(slots) * P * 4, s));
-        ctx->pp_posmap_P = P;
-        ctx->pp_posmap_slots = slots;
+    if (pp.posmap_P < P || pp.posmap_slots < slots) {
+        pp.d_posmap.release();
+        pp.d_posmap.reserve(static_cast<size_t>(slots) * P * 4 + 8);
+        MC_HIP(hipMemsetAsync(pp.d_posmap.ptr, 0xFF, static_cast<size_t>(slots) * P * 4, s));
+        pp.posmap_P = P;
+        pp.posmap_slots = slots;
     }
     r.hit.reserve(H * 8 + 8);
     r.cvid.reserve(E * 4 + 8);
@@ -146,7 +148,7 @@ void pp_filter(mc_ctx *ctx, PPRun &r, int K)
         if (N) hipLaunchKernelGGL(mc::k_pp_filter, dim3(slots), dim3(256), 0, s, N, r.dorder.as<int>(), r.tick.as<int>() + 1,
                                   r.pr, a.FW, P, a.npoff, a.npts, a.nvf, r.hoff.as<int64_t>(), a.qoff, a.qm, r.qfp.as<int>(),
                                   a.mask_off, a.mask_pts, a.pfm, r.xyz.as<double>(), r.lab.as<int>(), r.ccnt.as<int>(),
-                                  r.nob.as<int>(), r.nsh.as<int>(), r.obase.as<int>(), ctx->d_pp_posmap.as<int>(),
+                                  r.nob.as<int>(), r.nsh.as<int>(), r.obase.as<int>(), pp.d_posmap.as<int>(),
                                   r.hit.as<unsigned long long>(), r.cvid.as<int>(), r.qobj.as<int>(), r.qcov.as<double>(),
                                   r.onm.as<int>(), r.onv.as<int>(), r.obox.as<double>(), r.eobj.as<int>());
         MC_HIP(hipGetLastError());
@@ -228,32 +230,33 @@ std::vector<uint8_t> pp_merge(mc_ctx *ctx, PPRun &r, int K, const mc::PPKept &ke
 void pp_publish(mc_ctx *ctx, PPRun &r, const std::vector<int32_t> &base, const mc::PPKept &kept,
                 const std::vector<uint8_t> &inv, bool host_results)
 {
+    PpState &pp = ctx->pp;
     const int N = r.a.N, K = base[N], Kk = static_cast<int>(kept.kept.size());
-    ctx->pp_state.assign(K, 0);
+    pp.state.assign(K, 0);
     int nfin = 0;
     for (int i = 0; i < Kk; i++) {
-        ctx->pp_state[kept.kept[i]] = inv[i] ? 1 : 2;
+        pp.state[kept.kept[i]] = inv[i] ? 1 : 2;
         nfin += inv[i] ? 0 : 1;
     }
-    ctx->pp_obj_node.resize(K);
+    pp.obj_node.resize(K);
     for (int k = 0; k < N; k++)
-        for (int o = base[k]; o < base[k + 1]; o++) ctx->pp_obj_node[o] = k;
-    ctx->pp_info = {K, Kk, nfin, r.a.E, r.a.Q};  // objects, filtered, final, entries, node masks
-    mc::pp_final_tables(ctx->pp_state, ctx->pp_obj_node, r.h_nv.data(), r.h_nm.data(), ctx->pp_fslot, ctx->pp_fin,
-                        ctx->pp_fin_node, ctx->pp_opoff, ctx->pp_omoff);
-    ctx->pp_box = std::move(r.h_box);
-    ctx->d_pp_eobj.swap(r.eobj);
-    ctx->d_pp_qobj.swap(r.qobj);
-    ctx->d_pp_qcov.swap(r.qcov);
-    ctx->pp_P = r.a.P;
-    ctx->pp_F = r.a.F;
-    ctx->pp_host = ctx->pp_export = false;
+        for (int o = base[k]; o < base[k + 1]; o++) pp.obj_node[o] = k;
+    pp.info = {K, Kk, nfin, r.a.E, r.a.Q};  // objects, filtered, final, entries, node masks
+    mc::pp_final_tables(pp.state, pp.obj_node, r.h_nv.data(), r.h_nm.data(), pp.fslot, pp.fin,
+                        pp.fin_node, pp.opoff, pp.omoff);
+    pp.box = std::move(r.h_box);
+    pp.d_eobj.swap(r.eobj);
+    pp.d_qobj.swap(r.qobj);
+    pp.d_qcov.swap(r.qcov);
+    pp.P = r.a.P;
+    pp.F = r.a.F;
+    pp.host = pp.have_export = false;
     if (host_results) pp_fetch_host(ctx);
     else {
         MC_HIP(hipStreamSynchronize(ctx->stream));
         ctx->timer.collect();
     }
-    ctx->have_pp = true;
+    pp.have = true;
 }
 
 // ---- the checked entry path ----
@@ -360,34 +363,35 @@ void pp_run(mc_ctx *ctx, PPRun &r, bool host_results)
 // the export arrays of the last post-processing result, built once per result
 void pp_build_export(mc_ctx *ctx)
 {
-    if (ctx->pp_export) return;
+    PpState &pp = ctx->pp;
+    if (pp.have_export) return;
     hipStream_t s = ctx->stream;
-    const int K = ctx->pp_info.num_objects, nf = ctx->pp_info.num_final;
-    const int64_t np = ctx->pp_opoff[nf], nm = ctx->pp_omoff[nf];
-    pp_upload(s, ctx->d_pp_fslot, ctx->pp_fslot.data(), static_cast<size_t>(K) * 4);
-    pp_upload(s, ctx->d_pp_finobj, ctx->pp_fin.data(), static_cast<size_t>(nf) * 4);
-    pp_upload(s, ctx->d_pp_finnode, ctx->pp_fin_node.data(), static_cast<size_t>(nf) * 4);
-    pp_upload(s, ctx->d_pp_opoff, ctx->pp_opoff.data(), static_cast<size_t>(nf + 1) * 8);
-    pp_upload(s, ctx->d_pp_omoff, ctx->pp_omoff.data(), static_cast<size_t>(nf + 1) * 8);
-    ctx->d_pp_opts.reserve(np * 4 + 8);
-    ctx->d_pp_omask.reserve(nm * 4 + 8);
-    ctx->d_pp_ocov.reserve(nm * 8 + 8);
-    ctx->d_pp_repre.reserve(static_cast<size_t>(nf) * 20 + 8);
+    const int K = pp.info.num_objects, nf = pp.info.num_final;
+    const int64_t np = pp.opoff[nf], nm = pp.omoff[nf];
+    pp_upload(s, pp.d_fslot, pp.fslot.data(), static_cast<size_t>(K) * 4);
+    pp_upload(s, pp.d_finobj, pp.fin.data(), static_cast<size_t>(nf) * 4);
+    pp_upload(s, pp.d_finnode, pp.fin_node.data(), static_cast<size_t>(nf) * 4);
+    pp_upload(s, pp.d_opoff, pp.opoff.data(), static_cast<size_t>(nf + 1) * 8);
+    pp_upload(s, pp.d_omoff, pp.omoff.data(), static_cast<size_t>(nf + 1) * 8);
+    pp.d_opts.reserve(np * 4 + 8);
+    pp.d_omask.reserve(nm * 4 + 8);
+    pp.d_ocov.reserve(nm * 8 + 8);
+    pp.d_repre.reserve(static_cast<size_t>(nf) * 20 + 8);
     if (nf) {
         mc::TimedScope ts(ctx->timer, s, "pp_export");
-        hipLaunchKernelGGL(mc::k_pp_ex_fill, dim3(std::min(nf, 4096)), dim3(256), 0, s, nf, ctx->d_pp_finobj.as<int>(),
-                           ctx->d_pp_finnode.as<int>(), ctx->d_pp_npoff.as<int64_t>(), ctx->d_pp_npts.as<int>(),
-                           ctx->d_pp_eobj.as<int>(), ctx->d_pp_qoff.as<int64_t>(), ctx->d_pp_qm.as<int>(),
-                           ctx->d_pp_qobj.as<int>(), ctx->d_pp_qcov.as<double>(), ctx->d_pp_opoff.as<int64_t>(),
-                           ctx->d_pp_opts.as<int>(), ctx->d_pp_omoff.as<int64_t>(), ctx->d_pp_omask.as<int>(),
-                           ctx->d_pp_ocov.as<double>());
+        hipLaunchKernelGGL(mc::k_pp_ex_fill, dim3(std::min(nf, 4096)), dim3(256), 0, s, nf, pp.d_finobj.as<int>(),
+                           pp.d_finnode.as<int>(), pp.d_npoff.as<int64_t>(), pp.d_npts.as<int>(),
+                           pp.d_eobj.as<int>(), pp.d_qoff.as<int64_t>(), pp.d_qm.as<int>(),
+                           pp.d_qobj.as<int>(), pp.d_qcov.as<double>(), pp.d_opoff.as<int64_t>(),
+                           pp.d_opts.as<int>(), pp.d_omoff.as<int64_t>(), pp.d_omask.as<int>(),
+                           pp.d_ocov.as<double>());
         hipLaunchKernelGGL(mc::k_pp_ex_repre, dim3(std::min(ceil_div(nf, 4), 4096)), dim3(256), 0, s, nf,
-                           ctx->d_pp_omoff.as<int64_t>(), ctx->d_pp_ocov.as<double>(), ctx->d_pp_repre.as<int>());
+                           pp.d_omoff.as<int64_t>(), pp.d_ocov.as<double>(), pp.d_repre.as<int>());
         MC_HIP(hipGetLastError());
     }
     MC_HIP(hipStreamSynchronize(s));  // the uploads read the context's host vectors
     ctx->timer.collect();
-    ctx->pp_export = true;
+    pp.have_export = true;
 }
 
 }  // namespace
@@ -400,7 +404,8 @@ int mc_pp_run(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points, int32
               const int64_t *node_mask_off, const int32_t *node_masks, const int32_t *node_mask_col)
 {
     return guarded(ctx, [&] {
-        ctx->have_pp = false;
+        PpState &pp = ctx->pp;
+        pp.have = false;
         PPRun r;
         mc::PPArgs &a = r.a;  // the host arrays for the checks, then their device copies
         a.P = num_points, a.F = num_frames, a.Mt = num_masks, a.N = num_nodes;
@@ -416,19 +421,19 @@ int mc_pp_run(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points, int32
         pp_upload(s, pfm, pfm_bits, static_cast<size_t>(a.P) * a.FW * 8);
         pp_upload(s, moff, mask_off, static_cast<size_t>(a.Mt + 1) * 8);
         pp_upload(s, mpts, mask_pts, static_cast<size_t>(a.MP) * 4);
-        pp_upload(s, ctx->d_pp_npoff, node_pt_off, static_cast<size_t>(a.N + 1) * 8);
-        pp_upload(s, ctx->d_pp_npts, node_pts, static_cast<size_t>(a.E) * 4);
+        pp_upload(s, pp.d_npoff, node_pt_off, static_cast<size_t>(a.N + 1) * 8);
+        pp_upload(s, pp.d_npts, node_pts, static_cast<size_t>(a.E) * 4);
         pp_upload(s, nvf, node_vf_bits, static_cast<size_t>(a.N) * a.FW * 8);
-        pp_upload(s, ctx->d_pp_qoff, node_mask_off, static_cast<size_t>(a.N + 1) * 8);
-        pp_upload(s, ctx->d_pp_qm, node_masks, static_cast<size_t>(a.Q) * 4);
+        pp_upload(s, pp.d_qoff, node_mask_off, static_cast<size_t>(a.N + 1) * 8);
+        pp_upload(s, pp.d_qm, node_masks, static_cast<size_t>(a.Q) * 4);
         pp_upload(s, qcol, node_mask_col, static_cast<size_t>(a.Q) * 4);
         a.scene = scene.as<double>();
         a.pfm = pfm.as<unsigned long long>(), a.nvf = nvf.as<unsigned long long>();
-        a.mask_off = moff.as<int64_t>(), a.npoff = ctx->d_pp_npoff.as<int64_t>(), a.qoff = ctx->d_pp_qoff.as<int64_t>();
-        a.mask_pts = mpts.as<int>(), a.npts = ctx->d_pp_npts.as<int>(), a.qm = ctx->d_pp_qm.as<int>();
+        a.mask_off = moff.as<int64_t>(), a.npoff = pp.d_npoff.as<int64_t>(), a.qoff = pp.d_qoff.as<int64_t>();
+        a.mask_pts = mpts.as<int>(), a.npts = pp.d_npts.as<int>(), a.qm = pp.d_qm.as<int>();
         a.qcol = qcol.as<int>();
         pp_run(ctx, r, true);
-        ctx->d_pp_qcol.swap(qcol);
+        pp.d_qcol.swap(qcol);
     });
 }
 
@@ -439,7 +444,8 @@ int mc_pp_run_device(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points
                      const int32_t *node_masks, const int32_t *node_mask_col)
 {
     return guarded(ctx, [&] {
-        ctx->have_pp = false;
+        PpState &pp = ctx->pp;
+        pp.have = false;
         PPRun r;
         mc::PPArgs &a = r.a;
         a.P = num_points, a.F = num_frames, a.Mt = num_masks, a.N = num_nodes;
@@ -450,14 +456,14 @@ int mc_pp_run_device(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points
         a.mask_pts = mask_pts, a.npts = node_pts, a.qm = node_masks, a.qcol = node_mask_col;
         pp_check_args(ctx, params, r, false);
         hipStream_t s = ctx->stream;  // the node arrays stay with the context for the export
-        pp_upload(s, ctx->d_pp_npoff, a.npoff, static_cast<size_t>(a.N + 1) * 8, hipMemcpyDeviceToDevice);
-        pp_upload(s, ctx->d_pp_npts, a.npts, static_cast<size_t>(a.E) * 4, hipMemcpyDeviceToDevice);
-        pp_upload(s, ctx->d_pp_qoff, a.qoff, static_cast<size_t>(a.N + 1) * 8, hipMemcpyDeviceToDevice);
-        pp_upload(s, ctx->d_pp_qm, a.qm, static_cast<size_t>(a.Q) * 4, hipMemcpyDeviceToDevice);
-        pp_upload(s, ctx->d_pp_qcol, a.qcol, static_cast<size_t>(a.Q) * 4, hipMemcpyDeviceToDevice);
-        a.npoff = ctx->d_pp_npoff.as<int64_t>(), a.npts = ctx->d_pp_npts.as<int>();
-        a.qoff = ctx->d_pp_qoff.as<int64_t>(), a.qm = ctx->d_pp_qm.as<int>();
-        a.qcol = ctx->d_pp_qcol.as<int>();
+        pp_upload(s, pp.d_npoff, a.npoff, static_cast<size_t>(a.N + 1) * 8, hipMemcpyDeviceToDevice);
+        pp_upload(s, pp.d_npts, a.npts, static_cast<size_t>(a.E) * 4, hipMemcpyDeviceToDevice);
+        pp_upload(s, pp.d_qoff, a.qoff, static_cast<size_t>(a.N + 1) * 8, hipMemcpyDeviceToDevice);
+        pp_upload(s, pp.d_qm, a.qm, static_cast<size_t>(a.Q) * 4, hipMemcpyDeviceToDevice);
+        pp_upload(s, pp.d_qcol, a.qcol, static_cast<size_t>(a.Q) * 4, hipMemcpyDeviceToDevice);
+        a.npoff = pp.d_npoff.as<int64_t>(), a.npts = pp.d_npts.as<int>();
+        a.qoff = pp.d_qoff.as<int64_t>(), a.qm = pp.d_qm.as<int>();
+        a.qcol = pp.d_qcol.as<int>();
         pp_run(ctx, r, false);
     });
 }
@@ -465,16 +471,20 @@ int mc_pp_run_device(mc_ctx *ctx, const mc_pp_params *params, int64_t num_points
 int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *scene_xyz, int scene_on_device)
 {
     return guarded(ctx, [&] {
-        ctx->have_pp = false;
-        MC_REQUIRE(ctx->have_cluster, MC_ERR_STATE, "no clustering result (mc_cluster_run first)");
-        MC_REQUIRE(ctx->nodes_from_graph, MC_ERR_STATE, "the nodes were given by mc_nodes_set: no mask table");
-        MC_REQUIRE(!sharded(ctx) || ctx->sh_pending == 0, MC_ERR_STATE, "this rank does not hold the full result");
-        MC_REQUIRE(scene_xyz || (ctx->bp.have_points && ctx->bp.P == ctx->P), MC_ERR_STATE,
+        SceneState &sc = ctx->scene;
+        GraphState &gr = ctx->graph;
+        ClusterState &cl = ctx->cluster;
+        PpState &pp = ctx->pp;
+        pp.have = false;
+        MC_REQUIRE(cl.have, MC_ERR_STATE, "no clustering result (mc_cluster_run first)");
+        MC_REQUIRE(gr.nodes_from_graph, MC_ERR_STATE, "the nodes were given by mc_nodes_set: no mask table");
+        MC_REQUIRE(!sharded(ctx) || ctx->shard.pending == 0, MC_ERR_STATE, "this rank does not hold the full result");
+        MC_REQUIRE(scene_xyz || (ctx->bp.have_points && ctx->bp.P == sc.P), MC_ERR_STATE,
                    "no scene points: pass scene_xyz or call mc_scene_set_points");
         sync_stats(ctx);
         hipStream_t s = ctx->stream;
-        const int K = ctx->K, N0 = ctx->N0, FW = ctx->FW, M = ctx->M, Min = ctx->M_in;
-        const int64_t P = ctx->P, np = ctx->h_stats[ST_NPTS];
+        const int K = cl.K, N0 = gr.N0, FW = sc.FW, M = sc.M, Min = sc.M_in;
+        const int64_t P = sc.P, np = ctx->h_stats[ST_NPTS];
         DevBuf scene, moff, mlen, cnt, keepf, nid, dnn, sel, plen, qlen, inidx, nvf, qcol;
         const double *d_scene = scene_xyz;
         {
@@ -493,13 +503,13 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
             const int *d_inidx = nullptr;
             if (M != Min) {
                 inidx.reserve(static_cast<size_t>(M) * 4 + 8);
-                if (M) MC_HIP(hipMemcpyAsync(inidx.ptr, ctx->h_in_index.data(), static_cast<size_t>(M) * 4, hipMemcpyHostToDevice, s));
+                if (M) MC_HIP(hipMemcpyAsync(inidx.ptr, sc.h_in_index.data(), static_cast<size_t>(M) * 4, hipMemcpyHostToDevice, s));
                 d_inidx = inidx.as<int>();
             }
             mlen.reserve(static_cast<size_t>(Min) * 4 + 8);
             moff.reserve(static_cast<size_t>(Min + 1) * 8);
             MC_HIP(hipMemsetAsync(mlen.ptr, 0, static_cast<size_t>(Min) * 4 + 4, s));
-            if (M) hipLaunchKernelGGL(mc::k_pp_cl_masklen, grid_for(M), dim3(256), 0, s, M, d_inidx, ctx->d_mask_off.as<int>(),
+            if (M) hipLaunchKernelGGL(mc::k_pp_cl_masklen, grid_for(M), dim3(256), 0, s, M, d_inidx, sc.d_mask_off.as<int>(),
                                       mlen.as<int>());
             hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, mlen.as<int>(), Min, moff.as<int64_t>());
             // nodes: the objects with at least 2 level-0 masks, in object order
@@ -508,7 +518,7 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
             nid.reserve(static_cast<size_t>(K + 1) * 4 + 8);
             dnn.reserve(8);
             MC_HIP(hipMemsetAsync(cnt.ptr, 0, static_cast<size_t>(K) * 4 + 4, s));
-            if (N0) hipLaunchKernelGGL(mc::k_pp_cl_count, grid_for(N0), dim3(256), 0, s, N0, ctx->d_final_label.as<int>(),
+            if (N0) hipLaunchKernelGGL(mc::k_pp_cl_count, grid_for(N0), dim3(256), 0, s, N0, cl.d_final_label.as<int>(),
                                        cnt.as<int>());
             if (K) hipLaunchKernelGGL(mc::k_pp_cl_keep, grid_for(K), dim3(256), 0, s, K, cnt.as<int>(), keepf.as<int>());
             mc::scan_device_n(s, keepf.as<int>(), nid.as<int>(), nullptr, K, dnn.as<int>());
@@ -523,50 +533,51 @@ int mc_pp_run_clustered(mc_ctx *ctx, const mc_pp_params *params, const double *s
         qlen.reserve(static_cast<size_t>(Nn) * 4 + 8);
         nvf.reserve(static_cast<size_t>(Nn) * FW * 8 + 8);
         qcol.reserve(static_cast<size_t>(N0) * 4 + 8);
-        ctx->d_pp_npoff.reserve(static_cast<size_t>(Nn + 1) * 8);
-        ctx->d_pp_qoff.reserve(static_cast<size_t>(Nn + 1) * 8);
-        ctx->d_pp_npts.reserve(static_cast<size_t>(np) * 4 + 8);
-        ctx->d_pp_qm.reserve(static_cast<size_t>(N0) * 4 + 8);
+        pp.d_npoff.reserve(static_cast<size_t>(Nn + 1) * 8);
+        pp.d_qoff.reserve(static_cast<size_t>(Nn + 1) * 8);
+        pp.d_npts.reserve(static_cast<size_t>(np) * 4 + 8);
+        pp.d_qm.reserve(static_cast<size_t>(N0) * 4 + 8);
         {
             mc::TimedScope ts(ctx->timer, s, "pp_prep");
             if (K) hipLaunchKernelGGL(mc::k_pp_cl_select, grid_for(K), dim3(256), 0, s, K, cnt.as<int>(), nid.as<int>(),
-                                      ctx->d_ptoff_out.as<int>(), sel.as<int>(), plen.as<int>(), qlen.as<int>());
-            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, plen.as<int>(), Nn, ctx->d_pp_npoff.as<int64_t>());
-            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, qlen.as<int>(), Nn, ctx->d_pp_qoff.as<int64_t>());
+                                      cl.d_ptoff_out.as<int>(), sel.as<int>(), plen.as<int>(), qlen.as<int>());
+            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, plen.as<int>(), Nn, pp.d_npoff.as<int64_t>());
+            hipLaunchKernelGGL(mc::k_pp_scan64<int>, dim3(1), dim3(1024), 0, s, qlen.as<int>(), Nn, pp.d_qoff.as<int64_t>());
             if (Nn) {
                 hipLaunchKernelGGL(mc::k_pp_cl_members, dim3(std::min(ceil_div(Nn, 4), 4096)), dim3(256), 0, s, Nn, N0,
-                                   sel.as<int>(), ctx->d_final_label.as<int>(), ctx->d_node0_g.as<int>(),
-                                   M != Min ? inidx.as<int>() : nullptr, ctx->d_mask_col.as<int>(),
-                                   ctx->d_pp_qoff.as<int64_t>(), ctx->d_pp_qm.as<int>(), qcol.as<int>());
+                                   sel.as<int>(), cl.d_final_label.as<int>(), gr.d_node0_g.as<int>(),
+                                   M != Min ? inidx.as<int>() : nullptr, sc.d_mask_col.as<int>(),
+                                   pp.d_qoff.as<int64_t>(), pp.d_qm.as<int>(), qcol.as<int>());
                 hipLaunchKernelGGL(mc::k_pp_cl_gather, dim3(std::min(Nn, 4096)), dim3(256), 0, s, Nn, FW, sel.as<int>(),
-                                   ctx->d_ptoff_out.as<int>(), ctx->d_pts_out.as<int>(), ctx->fin.vf,
-                                   ctx->d_pp_npoff.as<int64_t>(), ctx->d_pp_npts.as<int>(), nvf.as<unsigned long long>());
+                                   cl.d_ptoff_out.as<int>(), cl.d_pts_out.as<int>(), cl.fin.vf,
+                                   pp.d_npoff.as<int64_t>(), pp.d_npts.as<int>(), nvf.as<unsigned long long>());
             }
             MC_HIP(hipGetLastError());
         }
         PPRun r;
         mc::PPArgs &a = r.a;
-        a.P = P, a.F = ctx->F, a.Mt = Min, a.N = Nn;
+        a.P = P, a.F = sc.F, a.Mt = Min, a.N = Nn;
         a.scene = d_scene;
-        a.pfm = ctx->d_pfm.as<unsigned long long>();
+        a.pfm = gr.d_pfm.as<unsigned long long>();
         a.nvf = nvf.as<unsigned long long>();
-        a.mask_off = moff.as<int64_t>(), a.npoff = ctx->d_pp_npoff.as<int64_t>(), a.qoff = ctx->d_pp_qoff.as<int64_t>();
-        a.mask_pts = ctx->d_mask_pts.as<int>(), a.npts = ctx->d_pp_npts.as<int>(), a.qm = ctx->d_pp_qm.as<int>();
+        a.mask_off = moff.as<int64_t>(), a.npoff = pp.d_npoff.as<int64_t>(), a.qoff = pp.d_qoff.as<int64_t>();
+        a.mask_pts = sc.d_mask_pts.as<int>(), a.npts = pp.d_npts.as<int>(), a.qm = pp.d_qm.as<int>();
         a.qcol = qcol.as<int>();
         pp_check_args(ctx, params, r, false);
         pp_run(ctx, r, false);
-        ctx->d_pp_qcol.swap(qcol);
+        pp.d_qcol.swap(qcol);
     });
 }
 
 int mc_pp_export_info(mc_ctx *ctx, int32_t *num_final, int64_t *num_points, int64_t *num_masks)
 {
     return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        const int nf = ctx->pp_info.num_final;
+        PpState &pp = ctx->pp;
+        MC_REQUIRE(pp.have, MC_ERR_STATE, "no post-processing result");
+        const int nf = pp.info.num_final;
         if (num_final) *num_final = nf;
-        if (num_points) *num_points = ctx->pp_opoff[nf];
-        if (num_masks) *num_masks = ctx->pp_omoff[nf];
+        if (num_points) *num_points = pp.opoff[nf];
+        if (num_masks) *num_masks = pp.omoff[nf];
     });
 }
 
@@ -574,22 +585,23 @@ int mc_pp_export(mc_ctx *ctx, int64_t *obj_pt_off, int32_t *obj_pts, int64_t *ob
                  double *obj_mask_cov, int32_t *obj_repre, int32_t *obj_node, int on_device)
 {
     return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
+        PpState &pp = ctx->pp;
+        MC_REQUIRE(pp.have, MC_ERR_STATE, "no post-processing result");
         pp_build_export(ctx);
         hipStream_t s = ctx->stream;
-        const int nf = ctx->pp_info.num_final;
-        const int64_t np = ctx->pp_opoff[nf], nm = ctx->pp_omoff[nf];
+        const int nf = pp.info.num_final;
+        const int64_t np = pp.opoff[nf], nm = pp.omoff[nf];
         auto cp = [&](void *dst, const DevBuf &src, size_t bytes) {
             if (dst && bytes)
                 MC_HIP(hipMemcpyAsync(dst, src.ptr, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         };
-        cp(obj_pt_off, ctx->d_pp_opoff, static_cast<size_t>(nf + 1) * 8);
-        cp(obj_pts, ctx->d_pp_opts, static_cast<size_t>(np) * 4);
-        cp(obj_mask_off, ctx->d_pp_omoff, static_cast<size_t>(nf + 1) * 8);
-        cp(obj_masks, ctx->d_pp_omask, static_cast<size_t>(nm) * 4);
-        cp(obj_mask_cov, ctx->d_pp_ocov, static_cast<size_t>(nm) * 8);
-        cp(obj_repre, ctx->d_pp_repre, static_cast<size_t>(nf) * 20);
-        cp(obj_node, ctx->d_pp_finnode, static_cast<size_t>(nf) * 4);
+        cp(obj_pt_off, pp.d_opoff, static_cast<size_t>(nf + 1) * 8);
+        cp(obj_pts, pp.d_opts, static_cast<size_t>(np) * 4);
+        cp(obj_mask_off, pp.d_omoff, static_cast<size_t>(nf + 1) * 8);
+        cp(obj_masks, pp.d_omask, static_cast<size_t>(nm) * 4);
+        cp(obj_mask_cov, pp.d_ocov, static_cast<size_t>(nm) * 8);
+        cp(obj_repre, pp.d_repre, static_cast<size_t>(nf) * 20);
+        cp(obj_node, pp.d_finnode, static_cast<size_t>(nf) * 4);
         MC_HIP(hipStreamSynchronize(s));
     });
 }
@@ -597,11 +609,12 @@ int mc_pp_export(mc_ctx *ctx, int64_t *obj_pt_off, int32_t *obj_pts, int64_t *ob
 int mc_pp_export_pred_masks(mc_ctx *ctx, uint8_t *out, int on_device)
 {
     return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
+        PpState &pp = ctx->pp;
+        MC_REQUIRE(pp.have, MC_ERR_STATE, "no post-processing result");
         pp_build_export(ctx);
         hipStream_t s = ctx->stream;
-        const int nf = ctx->pp_info.num_final;
-        const int64_t P = ctx->pp_P, E = ctx->pp_info.num_entries;
+        const int nf = pp.info.num_final;
+        const int64_t P = pp.P, E = pp.info.num_entries;
         const size_t bytes = static_cast<size_t>(P) * nf;
         if (!bytes) return;
         MC_REQUIRE(out, MC_ERR_INVALID, "null argument");
@@ -614,8 +627,8 @@ int mc_pp_export_pred_masks(mc_ctx *ctx, uint8_t *out, int on_device)
         MC_HIP(hipMemsetAsync(d, 0, bytes, s));
         {
             mc::TimedScope ts(ctx->timer, s, "pp_export");
-            hipLaunchKernelGGL(mc::k_pp_ex_pred, grid_for(E), dim3(256), 0, s, E, ctx->d_pp_npts.as<int>(),
-                               ctx->d_pp_eobj.as<int>(), ctx->d_pp_fslot.as<int>(), nf, d);
+            hipLaunchKernelGGL(mc::k_pp_ex_pred, grid_for(E), dim3(256), 0, s, E, pp.d_npts.as<int>(),
+                               pp.d_eobj.as<int>(), pp.d_fslot.as<int>(), nf, d);
             MC_HIP(hipGetLastError());
         }
         if (!on_device) MC_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, s));
@@ -627,9 +640,9 @@ int mc_pp_export_pred_masks(mc_ctx *ctx, uint8_t *out, int on_device)
 int mc_pp_get_info(mc_ctx *ctx, mc_pp_info *info)
 {
     return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
+        MC_REQUIRE(ctx->pp.have, MC_ERR_STATE, "no post-processing result");
         MC_REQUIRE(info, MC_ERR_INVALID, "null argument");
-        *info = ctx->pp_info;
+        *info = ctx->pp.info;
     });
 }
 
@@ -637,17 +650,18 @@ int mc_pp_get_results(mc_ctx *ctx, int32_t *entry_object, int32_t *mask_object, 
                       uint8_t *object_state, int32_t *object_node, double *object_bbox)
 {
     return guarded(ctx, [&] {
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
+        PpState &pp = ctx->pp;
+        MC_REQUIRE(pp.have, MC_ERR_STATE, "no post-processing result");
         if (entry_object || mask_object || mask_coverage) pp_fetch_host(ctx);
         auto cp = [](void *dst, const void *src, size_t bytes) {
             if (dst && bytes) std::memcpy(dst, src, bytes);
         };
-        cp(entry_object, ctx->pp_entry_obj.data(), ctx->pp_entry_obj.size() * 4);
-        cp(mask_object, ctx->pp_qobj.data(), ctx->pp_qobj.size() * 4);
-        cp(mask_coverage, ctx->pp_qcov.data(), ctx->pp_qcov.size() * 8);
-        cp(object_state, ctx->pp_state.data(), ctx->pp_state.size());
-        cp(object_node, ctx->pp_obj_node.data(), ctx->pp_obj_node.size() * 4);
-        cp(object_bbox, ctx->pp_box.data(), ctx->pp_box.size() * 8);
+        cp(entry_object, pp.entry_obj.data(), pp.entry_obj.size() * 4);
+        cp(mask_object, pp.qobj.data(), pp.qobj.size() * 4);
+        cp(mask_coverage, pp.qcov.data(), pp.qcov.size() * 8);
+        cp(object_state, pp.state.data(), pp.state.size());
+        cp(object_node, pp.obj_node.data(), pp.obj_node.size() * 4);
+        cp(object_bbox, pp.box.data(), pp.box.size() * 8);
     });
 }
 

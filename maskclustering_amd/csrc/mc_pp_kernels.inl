@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256) void k_pp_gather(const double *__restrict__ sc
 }
 
 // block min / max of 3 doubles over NT threads, broadcast; red holds 6 * NT/64 doubles
+// (restates block_minmax3 of mc_bp_common.inl for NT threads)
 template <int NT>
 __device__ __forceinline__ void pp_block_minmax3(double mn[3], double mx[3], double *red)
 {

@@ -181,14 +181,15 @@ int mc_proj_top_views(mc_ctx *ctx, const double *points, int32_t num_frames, con
                       int out_on_device)
 {
     return guarded(ctx, [&] {
+        PpState &pp = ctx->pp;
         MC_REQUIRE(top_k >= 1 && top_k <= mc::kProjMaxTop, MC_ERR_INVALID, "top_k outside [1, 16]");
         proj_check_camera(num_frames, width, height);
-        MC_REQUIRE(ctx->have_pp, MC_ERR_STATE, "no post-processing result");
-        MC_REQUIRE(num_frames >= ctx->pp_F, MC_ERR_INVALID, "fewer frames than the post-processed scene has");
-        const int64_t P = ctx->pp_P;
+        MC_REQUIRE(pp.have, MC_ERR_STATE, "no post-processing result");
+        MC_REQUIRE(num_frames >= pp.F, MC_ERR_INVALID, "fewer frames than the post-processed scene has");
+        const int64_t P = pp.P;
         MC_REQUIRE(points || (ctx->bp.have_points && ctx->bp.P == P), MC_ERR_STATE,
                    "no points: pass points or call mc_scene_set_points");
-        const int nf = ctx->pp_info.num_final, F = num_frames;
+        const int nf = pp.info.num_final, F = num_frames;
         if (!nf) return;
         MC_REQUIRE(intrinsics && world_to_cam && top_pos && top_frame && boxes && status, MC_ERR_INVALID, "null argument");
         MC_REQUIRE(static_cast<int64_t>(nf) * top_k <= (1 << 30), MC_ERR_UNSUPPORTED, "too many requests");
@@ -196,9 +197,9 @@ int mc_proj_top_views(mc_ctx *ctx, const double *points, int32_t num_frames, con
         ProjState &q = ctx->proj;
         hipStream_t s = ctx->stream;
         const int n = nf * top_k;
-        const int64_t nm = ctx->pp_omoff[nf];
+        const int64_t nm = pp.omoff[nf];
         int64_t mx = 0;
-        for (int f = 0; f < nf; f++) mx = std::max(mx, ctx->pp_opoff[f + 1] - ctx->pp_opoff[f]);
+        for (int f = 0; f < nf; f++) mx = std::max(mx, pp.opoff[f + 1] - pp.opoff[f]);
         const double *dp = proj_points(ctx, P, points, on_device), *dintr, *dw2c;
         proj_camera(ctx, F, intrinsics, world_to_cam, on_device, dintr, dw2c);
         int *dpos = top_pos, *dfr = top_frame, *dbox = boxes, *dstat = status, *dins = inside;
@@ -214,15 +215,15 @@ int mc_proj_top_views(mc_ctx *ctx, const double *points, int32_t num_frames, con
         q.ocol.reserve(static_cast<size_t>(nm) * 4 + 8);
         {
             TimedScope ts(ctx->timer, s, "proj_select");
-            hipLaunchKernelGGL(mc::k_proj_ocol, dim3(std::min(nf, 4096)), dim3(256), 0, s, nf, ctx->d_pp_finobj.as<int>(),
-                               ctx->d_pp_finnode.as<int>(), ctx->d_pp_qoff.as<int64_t>(), ctx->d_pp_qobj.as<int>(),
-                               ctx->d_pp_qcol.as<int>(), ctx->d_pp_omoff.as<int64_t>(), q.ocol.as<int>());
+            hipLaunchKernelGGL(mc::k_proj_ocol, dim3(std::min(nf, 4096)), dim3(256), 0, s, nf, pp.d_finobj.as<int>(),
+                               pp.d_finnode.as<int>(), pp.d_qoff.as<int64_t>(), pp.d_qobj.as<int>(),
+                               pp.d_qcol.as<int>(), pp.d_omoff.as<int64_t>(), q.ocol.as<int>());
             hipLaunchKernelGGL(mc::k_proj_top_select, dim3(std::min(ceil_div(nf, 4), 4096)), dim3(256), 0, s, nf, top_k,
-                               ctx->d_pp_omoff.as<int64_t>(), ctx->d_pp_ocov.as<double>(), q.ocol.as<int>(), dpos, dfr);
+                               pp.d_omoff.as<int64_t>(), pp.d_ocov.as<double>(), q.ocol.as<int>(), dpos, dfr);
             MC_HIP(hipGetLastError());
         }
-        proj_launch(ctx, n, nf, proj_parts(mx), nullptr, nullptr, top_k, dfr, nullptr, ctx->d_pp_opoff.as<int64_t>(),
-                    ctx->d_pp_opts.as<int>(), dp, dintr, dw2c, width, height, dfr, dbox, dstat, dins);
+        proj_launch(ctx, n, nf, proj_parts(mx), nullptr, nullptr, top_k, dfr, nullptr, pp.d_opoff.as<int64_t>(),
+                    pp.d_opts.as<int>(), dp, dintr, dw2c, width, height, dfr, dbox, dstat, dins);
         if (!out_on_device) {
             MC_HIP(hipMemcpyAsync(top_pos, dpos, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, s));
             MC_HIP(hipMemcpyAsync(top_frame, dfr, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, s));

@@ -1,55 +1,60 @@
 // mc_shard_host.inl — row-block sharding over processes: the host side (included by
 // mc_api.hip, same translation unit; kernels in mc_shard_kernels.inl).  A sharded mc_graph_build /
-// mc_cluster_run stops at an exchange (sh_pending); shard_export packs this rank's block and
+// mc_cluster_run stops at an exchange (shard.pending); shard_export packs this rank's block and
 // shard_import takes all ranks' blocks and runs the next steps of mc_graph_host.inl /
 // mc_cluster_host.inl.  The host moves the blocks (mc_shard_export / mc_shard_import), or, with a
 // communicator attached, shard_drain_native does over RCCL, loaded on first use.
 namespace {
 
-bool sharded(const mc_ctx *ctx) { return ctx->sh_world > 1 || ctx->comm; }
+bool sharded(const mc_ctx *ctx) { return ctx->shard.world > 1 || ctx->shard.comm; }
 
 // this context is `rank` of `world` from now on: no exchange pending, its rows and S3 lists rebuilt
 void shard_reset(mc_ctx *ctx, int rank, int world)
 {
-    ctx->sh_rank = rank;
-    ctx->sh_world = world;
-    ctx->sh_pending = 0;
-    if (ctx->have_scene) build_s3_lists(ctx, mc::frame_starts(ctx->h_col.data(), ctx->M, ctx->F));
+    SceneState &sc = ctx->scene;
+    ShardState &sh = ctx->shard;
+    sh.rank = rank;
+    sh.world = world;
+    sh.pending = 0;
+    if (sc.have) build_s3_lists(ctx, mc::frame_starts(sc.h_col.data(), sc.M, sc.F));
 }
 
 void shard_export(mc_ctx *ctx, int32_t phase, void *dst_dev, int64_t *bytes)
 {
+    GraphState &gr = ctx->graph;
+    ClusterState &cl = ctx->cluster;
+    ShardState &sh = ctx->shard;
     MC_REQUIRE(bytes, MC_ERR_INVALID, "null bytes");
-    MC_REQUIRE(phase == ctx->sh_pending && phase != 0, MC_ERR_STATE, "no such exchange pending");
+    MC_REQUIRE(phase == sh.pending && phase != 0, MC_ERR_STATE, "no such exchange pending");
     hipStream_t s = ctx->stream;
     if (phase == MC_SHARD_S3) {
-        const int nr = ctx->sh_r1 - ctx->sh_r0;
-        if (ctx->sh_s3_words < 0) {  // entry offsets of this rank's rows + their total (one host sync)
-            ctx->d_sh_eoff.reserve((nr + 2) * 4);
+        const int nr = sh.r1 - sh.r0;
+        if (sh.s3_words < 0) {  // entry offsets of this rank's rows + their total (one host sync)
+            sh.d_eoff.reserve((nr + 2) * 4);
             DevBuf dt;
             dt.reserve(8);
-            mc::scan_device_n(s, ctx->d_crow_len.as<int>() + ctx->sh_r0, ctx->d_sh_eoff.as<int>(), nullptr, nr,
+            mc::scan_device_n(s, gr.d_crow_len.as<int>() + sh.r0, sh.d_eoff.as<int>(), nullptr, nr,
                               dt.as<int>());
             int h = 0;
             MC_HIP(hipMemcpyAsync(&h, dt.ptr, 4, hipMemcpyDeviceToHost, s));
             MC_HIP(hipStreamSynchronize(s));
-            ctx->sh_s3_words = 2 + 2 * static_cast<int64_t>(nr) + h;
+            sh.s3_words = 2 + 2 * static_cast<int64_t>(nr) + h;
         }
-        *bytes = 4 * ctx->sh_s3_words;
+        *bytes = 4 * sh.s3_words;
         if (dst_dev)
             hipLaunchKernelGGL(mc::k_sh_s3_pack, grid_for(std::max(nr, 1) * 64, 256, 2048), dim3(256), 0, s,
-                               ctx->sh_r0, ctx->sh_r1, ctx->F, ctx->d_ctmp.as<int>(), ctx->d_crow_len.as<int>(),
-                               ctx->d_useg.as<unsigned char>(), ctx->d_sh_eoff.as<int>(), static_cast<int *>(dst_dev));
+                               sh.r0, sh.r1, ctx->scene.F, gr.d_ctmp.as<int>(), gr.d_crow_len.as<int>(),
+                               gr.d_useg.as<unsigned char>(), sh.d_eoff.as<int>(), static_cast<int *>(dst_dev));
     } else if (phase == MC_SHARD_HIST) {
-        *bytes = 8 * static_cast<int64_t>(ctx->F + 1);
+        *bytes = 8 * static_cast<int64_t>(ctx->scene.F + 1);
         if (dst_dev)
-            MC_HIP(hipMemcpyAsync(dst_dev, ctx->d_hist.ptr, *bytes, hipMemcpyDeviceToDevice, s));
+            MC_HIP(hipMemcpyAsync(dst_dev, gr.d_hist.ptr, *bytes, hipMemcpyDeviceToDevice, s));
     } else if (phase == MC_SHARD_FOREST) {
-        *bytes = 4 * (static_cast<int64_t>(ctx->N0) + 2);
+        *bytes = 4 * (static_cast<int64_t>(gr.N0) + 2);
         if (dst_dev)
-            hipLaunchKernelGGL(mc::k_sh_forest_export, grid_for(ctx->N0), dim3(256), 0, s, ctx->d_Nlev.as<int>(),
-                               ctx->d_parent.as<int>(), ctx->d_edges.as<unsigned long long>(),
-                               static_cast<int *>(dst_dev), ctx->N0);
+            hipLaunchKernelGGL(mc::k_sh_forest_export, grid_for(gr.N0), dim3(256), 0, s, cl.d_Nlev.as<int>(),
+                               cl.d_parent.as<int>(), cl.d_edges.as<unsigned long long>(),
+                               static_cast<int *>(dst_dev), gr.N0);
     } else {
         throw McError{MC_ERR_INVALID, "unknown exchange phase"};
     }
@@ -58,35 +63,39 @@ void shard_export(mc_ctx *ctx, int32_t phase, void *dst_dev, int64_t *bytes)
 
 void shard_import(mc_ctx *ctx, int32_t phase, const void *src_dev, int64_t stride_bytes)
 {
-    MC_REQUIRE(phase == ctx->sh_pending && phase != 0, MC_ERR_STATE, "no such exchange pending");
+    GraphState &gr = ctx->graph;
+    ClusterState &cl = ctx->cluster;
+    ShardState &sh = ctx->shard;
+    MC_REQUIRE(phase == sh.pending && phase != 0, MC_ERR_STATE, "no such exchange pending");
     MC_REQUIRE(src_dev, MC_ERR_INVALID, "null source");
     hipStream_t s = ctx->stream;
-    const int W = ctx->sh_world;
+    const int W = sh.world;
     if (phase == MC_SHARD_S3) {
         MC_REQUIRE(stride_bytes % 4 == 0 && stride_bytes >= 8, MC_ERR_INVALID, "bad S3 block stride");
         hipLaunchKernelGGL(mc::k_sh_s3_unpack, dim3(mc::kUnpackWg, W), dim3(256), 0, s,
-                           static_cast<const int *>(src_dev), static_cast<long long>(stride_bytes / 4), ctx->sh_rank,
-                           ctx->F, ctx->d_ctmp.as<int>(), ctx->d_crow_len.as<int>(), ctx->d_useg.as<unsigned char>());
+                           static_cast<const int *>(src_dev), static_cast<long long>(stride_bytes / 4), sh.rank,
+                           ctx->scene.F, gr.d_ctmp.as<int>(), gr.d_crow_len.as<int>(), gr.d_useg.as<unsigned char>());
         MC_HIP(hipGetLastError());
-        ctx->sh_pending = MC_SHARD_HIST;
+        sh.pending = MC_SHARD_HIST;
         graph_undo_s5_hist(ctx);  // undo + S5 replicated, this rank's S4 tiles
     } else if (phase == MC_SHARD_HIST) {
         // src: the histogram summed over the ranks
-        MC_HIP(hipMemcpyAsync(ctx->d_hist.ptr, src_dev, 8 * static_cast<size_t>(ctx->F + 1), hipMemcpyDeviceToDevice, s));
-        ctx->sh_pending = 0;
+        MC_HIP(hipMemcpyAsync(gr.d_hist.ptr, src_dev, 8 * static_cast<size_t>(ctx->scene.F + 1), hipMemcpyDeviceToDevice,
+                              s));
+        sh.pending = 0;
         graph_thresholds(ctx);
     } else if (phase == MC_SHARD_FOREST) {
-        MC_REQUIRE(stride_bytes % 4 == 0 && stride_bytes >= 4 * (static_cast<int64_t>(ctx->N0) + 2), MC_ERR_INVALID,
+        MC_REQUIRE(stride_bytes % 4 == 0 && stride_bytes >= 4 * (static_cast<int64_t>(gr.N0) + 2), MC_ERR_INVALID,
                    "bad FOREST block stride");
         {
             TimedScope ts(ctx->timer, s, "s6_pairs");
-            hipLaunchKernelGGL(mc::k_sh_forest_import, dim3(grid_for(ctx->N0, 256, 1024).x, W), dim3(256), 0, s,
-                               ctx->d_Nlev.as<int>(), static_cast<const int *>(src_dev),
-                               static_cast<long long>(stride_bytes / 4), ctx->sh_rank, ctx->N0,
-                               ctx->d_parent.as<int>(), ctx->d_edges.as<unsigned long long>());
+            hipLaunchKernelGGL(mc::k_sh_forest_import, dim3(grid_for(gr.N0, 256, 1024).x, W), dim3(256), 0, s,
+                               cl.d_Nlev.as<int>(), static_cast<const int *>(src_dev),
+                               static_cast<long long>(stride_bytes / 4), sh.rank, gr.N0,
+                               cl.d_parent.as<int>(), cl.d_edges.as<unsigned long long>());
         }
         MC_HIP(hipGetLastError());
-        ctx->sh_pending = 0;
+        sh.pending = 0;
         s6_levels(ctx, true);  // level 0's pairs are done: every rank's share, united above
     } else {
         throw McError{MC_ERR_INVALID, "unknown exchange phase"};
@@ -139,52 +148,54 @@ void rccl_check(ncclResult_t e, const char *what)
 // the block sizes, one host read), the HIST block all-reduced (sum, int64)
 void shard_drain_native(mc_ctx *ctx)
 {
+    ShardState &sh = ctx->shard;
     const Rccl &r = *rccl_lib();
     hipStream_t s = ctx->stream;
-    auto comm = static_cast<ncclComm_t>(ctx->comm);
-    const size_t W = static_cast<size_t>(ctx->sh_world);
-    while (ctx->sh_pending) {
-        const int ph = ctx->sh_pending;
+    auto comm = static_cast<ncclComm_t>(sh.comm);
+    const size_t W = static_cast<size_t>(sh.world);
+    while (sh.pending) {
+        const int ph = sh.pending;
         int64_t bytes = 0;
         shard_export(ctx, ph, nullptr, &bytes);
         if (ph == MC_SHARD_HIST) {
             const size_t n = static_cast<size_t>(bytes) / 8;
-            ctx->d_sh_send.reserve(n * 8);
-            ctx->d_sh_recv.reserve(n * 8);
-            shard_export(ctx, ph, ctx->d_sh_send.ptr, &bytes);
-            rccl_check(r.all_reduce(ctx->d_sh_send.ptr, ctx->d_sh_recv.ptr, n, ncclInt64, ncclSum, comm, s),
+            sh.d_send.reserve(n * 8);
+            sh.d_recv.reserve(n * 8);
+            shard_export(ctx, ph, sh.d_send.ptr, &bytes);
+            rccl_check(r.all_reduce(sh.d_send.ptr, sh.d_recv.ptr, n, ncclInt64, ncclSum, comm, s),
                        "ncclAllReduce (observer histogram)");
-            shard_import(ctx, ph, ctx->d_sh_recv.ptr, 0);
+            shard_import(ctx, ph, sh.d_recv.ptr, 0);
             continue;
         }
         int64_t n_max = bytes;
         if (ph == MC_SHARD_S3) {
-            ctx->d_sh_size.reserve(8);
-            MC_HIP(hipMemcpy(ctx->d_sh_size.ptr, &bytes, 8, hipMemcpyHostToDevice));  // done at return
-            rccl_check(r.all_reduce(ctx->d_sh_size.ptr, ctx->d_sh_size.ptr, 1, ncclInt64, ncclMax, comm, s),
+            sh.d_size.reserve(8);
+            MC_HIP(hipMemcpy(sh.d_size.ptr, &bytes, 8, hipMemcpyHostToDevice));  // done at return
+            rccl_check(r.all_reduce(sh.d_size.ptr, sh.d_size.ptr, 1, ncclInt64, ncclMax, comm, s),
                        "ncclAllReduce (S3 block size)");
-            MC_HIP(hipMemcpyAsync(&n_max, ctx->d_sh_size.ptr, 8, hipMemcpyDeviceToHost, s));
+            MC_HIP(hipMemcpyAsync(&n_max, sh.d_size.ptr, 8, hipMemcpyDeviceToHost, s));
             MC_HIP(hipStreamSynchronize(s));
         }
         const size_t words = static_cast<size_t>(std::max<int64_t>((n_max + 3) / 4, 1));
-        ctx->d_sh_send.reserve(words * 4);
-        ctx->d_sh_recv.reserve(W * words * 4);
-        MC_HIP(hipMemsetAsync(ctx->d_sh_send.ptr, 0, words * 4, s));
-        shard_export(ctx, ph, ctx->d_sh_send.ptr, &bytes);
-        rccl_check(r.all_gather(ctx->d_sh_send.ptr, ctx->d_sh_recv.ptr, words, ncclInt32, comm, s),
+        sh.d_send.reserve(words * 4);
+        sh.d_recv.reserve(W * words * 4);
+        MC_HIP(hipMemsetAsync(sh.d_send.ptr, 0, words * 4, s));
+        shard_export(ctx, ph, sh.d_send.ptr, &bytes);
+        rccl_check(r.all_gather(sh.d_send.ptr, sh.d_recv.ptr, words, ncclInt32, comm, s),
                    ph == MC_SHARD_S3 ? "ncclAllGather (S3 rows)" : "ncclAllGather (union-find forests)");
-        shard_import(ctx, ph, ctx->d_sh_recv.ptr, static_cast<int64_t>(4 * words));
+        shard_import(ctx, ph, sh.d_recv.ptr, static_cast<int64_t>(4 * words));
     }
 }
 
 void comm_detach(mc_ctx *ctx)
 {
-    if (ctx->comm && ctx->own_comm) {
+    ShardState &sh = ctx->shard;
+    if (sh.comm && sh.own_comm) {
         (void)hipStreamSynchronize(ctx->stream);
-        (void)rccl_lib()->comm_destroy(static_cast<ncclComm_t>(ctx->comm));
+        (void)rccl_lib()->comm_destroy(static_cast<ncclComm_t>(sh.comm));
     }
-    ctx->comm = nullptr;
-    ctx->own_comm = false;
+    sh.comm = nullptr;
+    sh.own_comm = false;
 }
 
 void comm_attach(mc_ctx *ctx, void *comm, bool own)
@@ -193,8 +204,8 @@ void comm_attach(mc_ctx *ctx, void *comm, bool own)
     rccl_check(rccl_lib()->comm_user_rank(static_cast<ncclComm_t>(comm), &rank), "ncclCommUserRank");
     rccl_check(rccl_lib()->comm_count(static_cast<ncclComm_t>(comm), &world), "ncclCommCount");
     comm_detach(ctx);
-    ctx->comm = comm;
-    ctx->own_comm = own;
+    ctx->shard.comm = comm;
+    ctx->shard.own_comm = own;
     shard_reset(ctx, rank, world);
 }
 
@@ -206,7 +217,8 @@ int mc_shard_set(mc_ctx *ctx, int32_t rank, int32_t world)
 {
     return guarded(ctx, [&] {
         MC_REQUIRE(world >= 1 && world <= 1024 && rank >= 0 && rank < world, MC_ERR_INVALID, "bad rank / world");
-        MC_REQUIRE(!ctx->comm, MC_ERR_STATE, "a communicator is attached (rank / world come from it; detach first)");
+        MC_REQUIRE(!ctx->shard.comm, MC_ERR_STATE,
+                   "a communicator is attached (rank / world come from it; detach first)");
         shard_reset(ctx, rank, world);
     });
 }
@@ -215,7 +227,7 @@ int mc_shard_pending(mc_ctx *ctx, int32_t *phase)
 {
     return guarded(ctx, [&] {
         MC_REQUIRE(phase, MC_ERR_INVALID, "null phase");
-        *phase = ctx->sh_pending;
+        *phase = ctx->shard.pending;
     });
 }
 

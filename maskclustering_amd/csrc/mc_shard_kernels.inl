@@ -1,5 +1,6 @@
 // mc_shard_kernels.inl — exchange blocks of the row-block sharded graph path,
-// included by mc_api.hip after mc_kernels.inl.
+// included by mc_api.hip after mc_kernels.inl (the block scans and spread counters: mc_dev_common.inl;
+// the union-find: mc_s6_columns.inl).
 //
 // One process per GPU.  S3 (graph/construction.py:98-135) runs on a contiguous block of mask rows
 // per rank, S4's observer histogram (:80-96) on every world-th tile, and the first S6 iteration
