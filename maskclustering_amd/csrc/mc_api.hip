@@ -112,6 +112,7 @@ int mc_ctx_create(int device, mc_ctx **out)
     int rc = guarded(ctx, [&] {
         MC_HIP(hipSetDevice(ctx->device));
         MC_HIP(hipDeviceGetAttribute(&ctx->num_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        MC_HIP(hipDeviceGetAttribute(&ctx->max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
         MC_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->own_stream = true;
         MC_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));

@@ -241,6 +241,7 @@ struct mc_ctx {
     int *h_stats = nullptr;  // pinned
     DevBuf d_stats;
     int num_cu = 256;
+    int max_lds = 64 * 1024;  // LDS one workgroup may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock)
 
     BpState bp;            // S1 back-projection (mc_bp_*)
     SceneState scene;      // the scene's masks (mc_scene_set_masks)

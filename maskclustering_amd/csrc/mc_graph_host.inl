@@ -6,8 +6,21 @@
 // mc_graph_plan.hpp's.
 namespace {
 
+constexpr size_t kHistTilesLds = 2 * mc::kHistTile * mc::kHistKW * sizeof(unsigned long long);
+
+// Both S4 kernels size their LDS by the frame count (mc_graph_plan.hpp).  A request above the
+// device's limit per workgroup is refused here, before any S4 launch, not left to the launch.
+void s4_require_lds(const mc_ctx *ctx, int F)
+{
+    const size_t limit = static_cast<size_t>(std::max(ctx->max_lds, 0));
+    MC_REQUIRE(mc::hist_lds_bytes(F, kHistTilesLds) <= limit, MC_ERR_UNSUPPORTED,
+               "observer histogram: the LDS for this many frames exceeds the device's limit per workgroup");
+    MC_REQUIRE(mc::thresholds_lds_bytes(F, mc::kS4ThrStaticLds) <= limit, MC_ERR_UNSUPPORTED,
+               "observer thresholds: the LDS for this many frames exceeds the device's limit per workgroup");
+}
+
 // S4 histogram launch: persistent blocks, R lane-indexed LDS replicas (odd stride)
-// rng: >= ceil(M / 64) int2 of scratch
+// rng: >= ceil(M / 64) int2 of scratch; the caller has passed s4_require_lds
 void launch_hist(hipStream_t s, const unsigned long long *vf, int M, int F, unsigned long long *hist, int2 *rng,
                  int shard_rank = 0, int shard_world = 1)
 {
@@ -17,7 +30,7 @@ void launch_hist(hipStream_t s, const unsigned long long *vf, int M, int F, unsi
     hipLaunchKernelGGL(mc::k_s4_ranges, grid_for(static_cast<int64_t>(nblk) * 64), dim3(256), 0, s, vf, M, FW, nblk, rng);
     const long long ntiles = static_cast<long long>(nblk) * (nblk + 1) / 2;
     const int HS = mc::hist_stride(F), R = mc::hist_replicas(F);
-    const size_t lds = 2 * mc::kHistTile * mc::kHistKW * sizeof(unsigned long long) + static_cast<size_t>(R) * HS * 4;
+    const size_t lds = mc::hist_lds_bytes(F, kHistTilesLds);
     const long long grid = std::min<long long>(ntiles, 1024);
     hipLaunchKernelGGL(mc::k_s4_hist, dim3(static_cast<unsigned>(grid)), dim3(256), lds, s, vf, M, FW, F, nblk, ntiles, R,
                        HS, rng, hist, shard_rank, shard_world);
@@ -269,7 +282,7 @@ void graph_thresholds(mc_ctx *ctx)
     int *stats = ctx->d_stats.as<int>();
     {
         TimedScope ts(ctx->timer, s, "s4_observer_hist");
-        hipLaunchKernelGGL(mc::k_s4_thresholds, dim3(1), dim3(256), (F + 1) * sizeof(unsigned long long), s,
+        hipLaunchKernelGGL(mc::k_s4_thresholds, dim3(1), dim3(256), mc::thresholds_lds_dynamic(F), s,
                            gr.d_hist.as<unsigned long long>(), F, gr.d_thr.as<float>(), gr.d_isint.as<int>(),
                            stats + ST_NTHR, stats + ST_THR_STATUS);
     }
@@ -323,6 +336,7 @@ int mc_graph_build(mc_ctx *ctx, const mc_graph_params *params)
         ShardState &sh = ctx->shard;
         MC_REQUIRE(ctx->scene.have, MC_ERR_STATE, "mc_graph_build before mc_scene_set_masks");
         MC_REQUIRE(params, MC_ERR_INVALID, "null params");
+        s4_require_lds(ctx, ctx->scene.F);
         ctx->cluster.have = false;
         ctx->graph.have = ctx->graph.have_nodes = false;
         sh.pending = 0;
@@ -474,6 +488,7 @@ int mc_observer_thresholds(mc_ctx *ctx, int32_t num_rows, int32_t num_frames, co
     return guarded(ctx, [&] {
         MC_REQUIRE(num_rows >= 0 && num_frames >= 0 && num_frames <= 16384, MC_ERR_INVALID, "bad sizes");
         MC_REQUIRE(thr && is_int && n && (num_rows == 0 || num_frames == 0 || vf_bits), MC_ERR_INVALID, "null argument");
+        s4_require_lds(ctx, num_frames);
         hipStream_t s = ctx->stream;
         const int M = num_rows, F = num_frames, FW = (F + 63) / 64;
         DevBuf vf, hist, dthr, disint, st;
@@ -487,9 +502,10 @@ int mc_observer_thresholds(mc_ctx *ctx, int32_t num_rows, int32_t num_frames, co
         DevBuf rng;
         rng.reserve((M / 64 + 2) * sizeof(int2));
         launch_hist(s, vf.as<unsigned long long>(), M, F, hist.as<unsigned long long>(), rng.as<int2>());
-        hipLaunchKernelGGL(mc::k_s4_thresholds, dim3(1), dim3(256), (F + 1) * sizeof(unsigned long long), s,
+        hipLaunchKernelGGL(mc::k_s4_thresholds, dim3(1), dim3(256), mc::thresholds_lds_dynamic(F), s,
                            hist.as<unsigned long long>(), F,
                            dthr.as<float>(), disint.as<int>(), st.as<int>(), st.as<int>() + 1);
+        MC_HIP(hipGetLastError());  // a refused launch is this call's error, not an unwritten status
         int hs[2];
         MC_HIP(hipMemcpyAsync(hs, st.ptr, 8, hipMemcpyDeviceToHost, s));
         MC_HIP(hipMemcpyAsync(thr, dthr.ptr, mc::kMaxThresholds * 4, hipMemcpyDeviceToHost, s));

@@ -12,7 +12,9 @@
 //    hold; each list largest first, ties in row order, so the long masks start early.
 //  * S4 replicas: the histogram kernel keeps R lane-indexed LDS copies of the F + 1 counters at an
 //    odd stride; R is the largest power of two up to 32 whose copies fit kHistReplicaBytes (1 when
-//    even one does not).
+//    even one does not).  hist_lds_bytes / thresholds_lds_bytes are the LDS the two S4 kernels ask for
+//    (dynamic + static); the host refuses a frame count whose request exceeds the device's limit
+//    per workgroup instead of launching (72 KiB and 130 KiB at 16384 frames).
 //  * S6 mode: connect_threshold <= 0 links every pair with enough observers (dense_obs); torch
 //    compares the rate in float32 (ctf); NaN passes no comparison, so it stays sparse with no edge.
 //  * Components route: levels t >= 1 of scenes up to kFusedComponentsMaxN0 level-0 nodes label the
@@ -120,6 +122,17 @@ inline int hist_replicas(int F)
     while (R > 1 && static_cast<size_t>(R) * hist_stride(F) * 4 > kHistReplicaBytes) R >>= 1;
     return R;
 }
+
+// k_s4_hist: the two staged tiles (tile_bytes) and the R replicas, all dynamic
+inline size_t hist_lds_bytes(int F, size_t tile_bytes)
+{
+    return tile_bytes + static_cast<size_t>(hist_replicas(F)) * hist_stride(F) * 4;
+}
+
+// k_s4_thresholds: F + 1 cumulative counts (u64, dynamic) beside its static arrays
+inline size_t thresholds_lds_dynamic(int F) { return (static_cast<size_t>(F) + 1) * 8; }
+
+inline size_t thresholds_lds_bytes(int F, size_t static_bytes) { return thresholds_lds_dynamic(F) + static_bytes; }
 
 struct S6Mode {
     bool dense_obs;

@@ -114,7 +114,8 @@ __device__ float cum_order_stat(const unsigned long long *cum, int F, unsigned l
     return static_cast<float>(lo);
 }
 
-// dynamic LDS: cum[F+1] (u64)
+// dynamic LDS: cum[F+1] (u64); static: part and pval (kS4ThrStaticLds, which the host's limit check adds)
+constexpr size_t kS4ThrStaticLds = 256 * sizeof(unsigned long long) + 20 * sizeof(float);
 __global__ __launch_bounds__(256) void k_s4_thresholds(const unsigned long long *__restrict__ hist, int F,
                                                        float *__restrict__ thr, int *__restrict__ is_int,
                                                        int *__restrict__ nthr, int *__restrict__ status)

@@ -123,6 +123,11 @@ __device__ void pairs_overflow_node(int a, const int *__restrict__ n_off, const 
             uf_unite(parent, a, bnode);
         }
     }
+    // The clears are relaxed stores: a barrier alone lets them still be in flight when the next node's
+    // adds, or (after the slot's release) another workgroup's, reach the same counters -- an add that finds
+    // the old count does not list its partner, and the late clear wipes the adds.  Every thread has its
+    // clears performed at device scope before the barrier.
+    __threadfence();
     __syncthreads();
 }
 
@@ -156,7 +161,7 @@ __device__ void pairs_overflow_local(OvfWork ow, const int *ovf_nodes, int novf,
     for (int q = 0; q < novf; q++)
         pairs_overflow_node(ovf_nodes[q], n_off, n_len, pool, coloff, collen, colnodes, nvf, FW, er, parent, scr, tl,
                             &ntouch, nedges, ec, t);
-    const int ne = block_sum<256>(static_cast<int>(nedges), ws);  // (its barriers order the clears before the release)
+    const int ne = block_sum<256>(static_cast<int>(nedges), ws);  // (every thread's clears are fenced; its barriers put them before the release)
     if (threadIdx.x == 0) {
         if (ne) spread_add(edges_t, static_cast<unsigned long long>(ne));
         atomicExch(&ow.locks[s_slot], 0);

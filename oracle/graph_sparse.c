@@ -36,6 +36,12 @@ static int cmp_i64(const void *a, const void *b)
     return x < y ? -1 : x > y;
 }
 
+static int cmp_i32(const void *a, const void *b)
+{
+    int32_t x = *(const int32_t *)a, y = *(const int32_t *)b;
+    return x < y ? -1 : x > y;
+}
+
 /* ------------------------------------------------------------------------ */
 /* S2 (construction.py:46-62).  Masks in frame order, ids ascending per frame.
  * kept[g] = 0 for the masks of a frame whose union is empty (:50-51).
@@ -127,7 +133,7 @@ int orcs_s3(int M_in, const int32_t *col, const int32_t *label, const int64_t *o
                     const int64_t cnt = j1 - j;
                     const int v = (int)(uint32_t)(keys[j] & 0xffffffff);
                     nz += cnt;
-                    if (cnt > bestc) { bestc = cnt; best = v; }   /* ascending labels: first max = smallest id (:122-123) */
+                    if (cnt > bestc) { bestc = cnt; best = v; }   /* keys ascend by label: first max = smallest id (:122-123) */
                     j = j1;
                 }
                 i = j;
@@ -137,15 +143,15 @@ int orcs_s3(int M_in, const int32_t *col, const int32_t *label, const int64_t *o
                 visible_num++;
                 const double contained_ratio = (double)bestc / (double)nz;        /* :124 */
                 if (contained_ratio > contained_threshold) {                      /* :125-128 */
-                    /* global index of (frame c, id best): masks of frame c are consecutive */
-                    int lo = 0, hi = M_in - 1, tgt = -1;
-                    while (lo <= hi) {
+                    /* global index of (frame c, id best): masks of frame c are consecutive, their ids in
+                     * any order (the first mask of the frame by bisection, then along the frame) */
+                    int lo = 0, hi = M_in, tgt = -1;
+                    while (lo < hi) {
                         const int mid = (lo + hi) / 2;
-                        const int64_t km = ((int64_t)col[mid] << 32) | (int64_t)(uint32_t)label[mid];
-                        const int64_t kk = ((int64_t)c << 32) | (int64_t)(uint32_t)best;
-                        if (km == kk) { tgt = mid; break; }
-                        if (km < kk) lo = mid + 1; else hi = mid - 1;
+                        if (col[mid] < c) lo = mid + 1; else hi = mid;
                     }
+                    for (int m = lo; m < M_in && col[m] == c; m++)
+                        if (label[m] == best) { tgt = m; break; }
                     ct_frame[(size_t)r * F_cap + n] = c;
                     ct_tgt[(size_t)r * F_cap + n] = gidx[tgt];
                     n++;
@@ -414,12 +420,17 @@ int orcs_cluster(int N0, int FW, int Mn, const uint64_t *vf0, const int64_t *c_o
                     const int i = mem[q];
                     for (int64_t e = coff[i]; e < coff[i + 1]; e++) buf[n++] = cidx[e];
                 }
-                /* sort + unique (insertion sort: rows are short, members already sorted) */
-                for (int64_t x = 1; x < n; x++) {
-                    const int32_t v = buf[x];
-                    int64_t y = x - 1;
-                    while (y >= 0 && buf[y] > v) { buf[y + 1] = buf[y]; y--; }
-                    buf[y + 1] = v;
+                /* sort + unique (insertion sort: rows are short, members already sorted; a component of
+                 * thousands of members with long rows -- masks seen in every frame -- would make it quadratic) */
+                if (n > 4096) {
+                    qsort(buf, (size_t)n, sizeof(int32_t), cmp_i32);
+                } else {
+                    for (int64_t x = 1; x < n; x++) {
+                        const int32_t v = buf[x];
+                        int64_t y = x - 1;
+                        while (y >= 0 && buf[y] > v) { buf[y + 1] = buf[y]; y--; }
+                        buf[y + 1] = v;
+                    }
                 }
                 int64_t u = 0;
                 for (int64_t x = 0; x < n; x++)

@@ -162,6 +162,10 @@ static void replica_cases()
     CHECK(hist_replicas(1) == 32 && hist_replicas(64) == 32 && hist_replicas(318) == 32);
     CHECK(hist_replicas(319) == 16 && hist_replicas(320) == 16);
     CHECK(fits(1, 10238) && !fits(1, 10239) && hist_replicas(16384) == 1);
+    // the LDS the two S4 kernels ask for: tile buffers + replicas; F + 1 cumulative counts + the static arrays
+    CHECK(hist_lds_bytes(318, 8192) == 8192 + 32 * 319 * 4 && hist_lds_bytes(16384, 8192) == 73732);
+    CHECK(thresholds_lds_dynamic(16384) == 131080 && thresholds_lds_bytes(16384, 2128) == 133208);
+    CHECK(thresholds_lds_bytes(16384, 2128) <= 160 * 1024 && hist_lds_bytes(16384, 8192) > 64 * 1024);
 }
 
 static void s6_cases()
