@@ -74,13 +74,19 @@ def dbscan(p: np.ndarray, eps: float, min_points: int) -> np.ndarray:
 
 
 def post_process_objects(scene, pfm, mask_pts, mask_col, nodes, point_filter_threshold,
-                         eps=0.1, min_points=4, overlapping_ratio=0.8):
+                         eps=0.1, min_points=4, overlapping_ratio=0.8, details=False):
     """scene f64 [P,3]; pfm bool [P,F]; mask_pts: list of int arrays (mask -> scene point ids);
     mask_col: frame column of each mask; nodes: list of (mask index list in mask_list order,
     vf bool [F], point id array in list(point_ids) order).
-    Returns (point id arrays, mask lists [(mask index, coverage)]) after the merge, in order."""
+    Returns (point id arrays, mask lists [(mask index, coverage)]) after the merge, in order.
+    details=True adds a third value, what the steps saw before the merge: ``nodes`` (per node with at
+    least 2 masks: its index, the class label of each point, per object its point positions, kept
+    flags and bbox, per mask its (object or -1, coverage)), ``pre_pts`` / ``pre_masks`` (the kept
+    objects' lists as the merge gets them), ``pre_obj`` (their (node record, object) pairs) and
+    ``invalid`` (the merge's flags)."""
     tot_pts, tot_box, tot_masks = [], [], []
-    for masks, vf, order in nodes:
+    seen, pre_obj = [], []
+    for node_index, (masks, vf, order) in enumerate(nodes):
         if len(masks) < 2:                                    # post_process.py:182
             continue
         order = np.asarray(order, np.int64)
@@ -92,6 +98,9 @@ def post_process_objects(scene, pfm, mask_pts, mask_col, nodes, point_filter_thr
         n_video = [pfm[order[o]][:, vcols].sum(axis=1) for o in objs]                 # :45-58
         hit = [np.zeros((len(o), len(vcols)), bool) for o in objs]
         obj_masks = [[] for _ in objs]
+        rec = dict(node=node_index, lab=lab, objs=objs, mask_best=[], valid=[],
+                   box=[(pts[o].min(axis=0), pts[o].max(axis=0)) for o in objs])
+        seen.append(rec)
         for m in masks:                                                               # :68-81
             fpos = np.nonzero(vcols == mask_col[m])[0]
             if len(fpos) == 0:
@@ -103,17 +112,20 @@ def post_process_objects(scene, pfm, mask_pts, mask_col, nodes, point_filter_thr
                 hit[i][w, fpos] = True
                 if len(w) > largest:
                     best, largest, cov = i, len(w), len(w) / len(o)
+            rec["mask_best"].append((best, cov))
             if largest == 0:
                 continue
             obj_masks[best].append((m, cov))
         for i, o in enumerate(objs):                                                  # :93-100
             ratio = hit[i].sum(axis=1) / (n_video[i] + 1e-6)
             valid = np.nonzero(ratio > point_filter_threshold)[0]
+            rec["valid"].append(ratio > point_filter_threshold)
             if len(valid) == 0 or len(obj_masks[i]) < 2:
                 continue
             tot_pts.append(order[o][valid])
             tot_box.append((pts[o].min(axis=0), pts[o].max(axis=0)))
             tot_masks.append(obj_masks[i])
+            pre_obj.append((len(seen) - 1, i))
     K = len(tot_pts)
     invalid = np.zeros(K, bool)
     sets = [set(p.tolist()) for p in tot_pts]
@@ -132,4 +144,7 @@ def post_process_objects(scene, pfm, mask_pts, mask_col, nodes, point_filter_thr
             elif inter / len(sets[j]) > overlapping_ratio:
                 invalid[j] = True
     keep = np.nonzero(~invalid)[0]
-    return [tot_pts[i] for i in keep], [tot_masks[i] for i in keep]
+    out = [tot_pts[i] for i in keep], [tot_masks[i] for i in keep]
+    if details:
+        return out + (dict(nodes=seen, pre_pts=tot_pts, pre_masks=tot_masks, pre_obj=pre_obj, invalid=invalid),)
+    return out

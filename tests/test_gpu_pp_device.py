@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import pp_oracle
+from pp_limit_inputs import pack_arrays as _pack_arrays
 from test_gpu_pp import synthetic_pp
 
 pytestmark = pytest.mark.gpu
@@ -52,20 +53,6 @@ def _packed(seed):
               for ml, vf, pts in nodes]
     return dict(scene=scene, pfm=pfm, fids=fids, mpc=mpc, nodes=nodes, keys=keys, mask_pts=mask_pts, mask_col=mask_col,
                 onodes=onodes, args=_pack_arrays(scene, pfm, mask_pts, mask_col, onodes))
-
-
-def _pack_arrays(scene, pfm, mask_pts, mask_col, onodes):
-    bits = _pp()._bits
-    F = pfm.shape[1]
-    nodes = [n for n in onodes if len(n[0]) >= 2]                    # post_process.py:182
-    off = lambda lens: np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)  # noqa: E731
-    cat = lambda arrs, dt: np.concatenate(arrs).astype(dt) if arrs else np.zeros(0, dt)  # noqa: E731
-    qm = cat([np.asarray(n[0], np.int64) for n in nodes], np.int32)
-    return dict(scene=np.ascontiguousarray(scene, np.float64), pfm=bits(pfm, F), F=F,
-                moff=off([len(p) for p in mask_pts]), mpts=cat(list(mask_pts), np.int32),
-                vf=bits(np.stack([n[1] for n in nodes]), F) if nodes else np.zeros((0, (F + 63) // 64), np.uint64),
-                poff=off([len(n[2]) for n in nodes]), pts=cat([n[2] for n in nodes], np.int32),
-                qoff=off([len(n[0]) for n in nodes]), qm=qm, qc=np.asarray(mask_col, np.int32)[qm])
 
 
 def _run_host(ctx, prm, a):
