@@ -1,12 +1,14 @@
 // mc_ap_host.inl — host side of the AP evaluation (mc_ev_*, include/mcgraph.h); kernels in
-// mc_ap_kernels.inl.  Included by mc_api.hip after the post-processing section.
+// mc_ap_kernels.inl.  Included by mc_api.hip after mc_pp_host.inl, whose pp_build_export it calls.
+// What the host decides without the GPU is mc_ap_plan.hpp: no function here that launches a kernel
+// checks a host table or parses buffer bytes.
 //
 // A scan reaches the accumulation in two halves.  mc_ev_add_scan* turn ground-truth ids and point
 // lists into the scan's compact tables on the device (instances, kept predictions, non-zero
-// same-class intersections) and fetch them: O(instances + predictions + pairs) words.  commit()
-// (shared with mc_ev_add_matches) lays the tables out per class, uploads them and runs the greedy
-// pass, which appends (score, true) examples to per-(scan, class, overlap) regions whose sizes
-// are known beforehand.  All checks come before the first write to the accumulation.
+// same-class intersections) and fetch them: O(instances + predictions + pairs) words.  ev_commit()
+// (shared with mc_ev_add_matches) checks the tables, lays them out per class, uploads them and runs
+// the greedy pass, which appends (score, true) examples to per-(scan, class, overlap) regions whose
+// sizes are known beforehand.  All checks come before the first write to the accumulation.
 //
 // mc_ev_state_*: the accumulation as a state buffer (per cell the distinct scores with their true /
 // false counts, hard false negatives, flags).  ev_runs() builds it on the device from the same cell
@@ -27,164 +29,128 @@ void ev_grow(DevBuf &b, size_t used, size_t need, hipStream_t s)
     b.swap(n);
 }
 
+// a message of mc_ap_plan.hpp as this call's error
+void ev_require(const char *msg, int code)
+{
+    if (msg) throw McError{code, msg};
+}
+
+// room for `add` more examples in U more units
+void ev_reserve_append(EvState &ev, int64_t add, int U, hipStream_t s)
+{
+    ev_grow(ev.d_ex_key, ev.ex_used * 8, (ev.ex_used + add) * 8 + 8, s);
+    ev_grow(ev.d_ex_true, ev.ex_used, ev.ex_used + add + 8, s);
+    ev_grow(ev.d_unit_cell, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
+    ev_grow(ev.d_unit_cnt, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
+    ev_grow(ev.d_unit_off, static_cast<size_t>(ev.units) * 8, static_cast<size_t>(ev.units + U) * 8 + 8, s);
+}
+
+// the planned scan's words to the device and the greedy pass over them (launches only)
+void ev_greedy_pass(mc_ctx *ctx, const EvTables &t, const mc::EvScanPlan &p)
+{
+    EvState &ev = ctx->ev;
+    hipStream_t s = ctx->stream;
+    const int G = static_cast<int>(t.gcls.size()), K = static_cast<int>(t.pcls.size()), A = p.A, O = ev.O;
+    const int64_t NP = static_cast<int64_t>(t.ppred.size());
+    const size_t words = p.words.size() - 1;
+    ev.d_words.reserve(words * 8 + 8);
+    MC_HIP(hipMemcpyAsync(ev.d_words.ptr, p.words.data(), words * 8, hipMemcpyHostToDevice, s));
+    const size_t b_q = static_cast<size_t>(NP) * 4, b_f = static_cast<size_t>(K) * 4, b_i = static_cast<size_t>(K) * 8,
+                 b_v = static_cast<size_t>(O) * K;
+    const size_t o_i = 0, o_q = o_i + b_i, o_f = o_q + ((b_q + 7) & ~size_t(7)), o_v = o_f + ((b_f + 7) & ~size_t(7));
+    ev.d_tmp.reserve(o_v + b_v + 8);
+    MC_HIP(hipMemsetAsync(ev.d_tmp.ptr, 0, o_v + b_v + 8, s));
+    const mc::EvWords<const int64_t> w = mc::ev_words(ev.d_words.as<const int64_t>(), G, K, NP, A);
+    char *T = ev.d_tmp.as<char>();
+    mc::EvScanDev d{};
+    d.G = G, d.K = K, d.NP = static_cast<int>(NP), d.A = A, d.O = O;
+    d.min_region = ev.min_region;
+    d.gvert = w.gvert, d.gid = w.gid, d.pvert = w.pvert, d.pvoid = w.pvoid, d.pslot = w.pslot;
+    d.pscore = reinterpret_cast<const double *>(w.pscore);
+    d.q_gt = w.q_gt, d.q_pred = w.q_pred, d.q_int = w.q_int;
+    d.s_p0 = w.s_p0, d.s_p1 = w.s_p1, d.s_nfilt = w.s_nfilt, d.s_npred = w.s_npred, d.s_cls = w.s_cls;
+    d.s_exoff = w.s_exoff, d.s_cap = w.s_cap;
+    d.overlaps = ev.d_overlaps.as<double>();
+    d.ign = reinterpret_cast<unsigned long long *>(T + o_i);
+    d.qmask = reinterpret_cast<unsigned *>(T + o_q);
+    d.found = reinterpret_cast<unsigned *>(T + o_f);
+    d.visited = reinterpret_cast<unsigned char *>(T + o_v);
+    d.ex_base = ev.ex_used, d.unit_base = ev.units;
+    d.ex_key = ev.d_ex_key.as<unsigned long long>(), d.ex_true = ev.d_ex_true.as<unsigned char>();
+    d.unit_cell = ev.d_unit_cell.as<int>(), d.unit_cnt = ev.d_unit_cnt.as<int>(), d.unit_off = ev.d_unit_off.as<int64_t>();
+    d.cell_hardfn = ev.d_hardfn.as<unsigned long long>(), d.cell_flags = ev.d_flags.as<unsigned>();
+    TimedScope ts(ctx->timer, s, "ev_greedy");
+    if (NP) hipLaunchKernelGGL(mc::k_ev_qual, grid_for(NP), dim3(256), 0, s, d);
+    hipLaunchKernelGGL(mc::k_ev_greedy, dim3(ceil_div(p.U, 4)), dim3(256), 0, s, d);
+    if (K) hipLaunchKernelGGL(mc::k_ev_fp, grid_for(static_cast<int64_t>(K) * O), dim3(256), 0, s, d);
+    MC_HIP(hipGetLastError());
+}
+
 void ev_commit(mc_ctx *ctx, EvTables &&t)
 {
     EvState &ev = ctx->ev;
     hipStream_t s = ctx->stream;
-    const int G = static_cast<int>(t.gcls.size()), K = static_cast<int>(t.pcls.size()), C = ev.C, O = ev.O;
-    const int64_t NP = static_cast<int64_t>(t.ppred.size());
-    for (int g = 0; g < G; g++) {
-        MC_REQUIRE(t.gcls[g] >= 0 && t.gcls[g] < C && (g == 0 || t.gcls[g] >= t.gcls[g - 1]), MC_ERR_INVALID,
-                   "ground-truth classes must be ascending class indices");
-        MC_REQUIRE(t.gvert[g] > 0, MC_ERR_INVALID, "ground-truth vert_count must be positive");
-    }
-    for (int k = 0; k < K; k++) {
-        MC_REQUIRE(t.pcls[k] >= 0 && t.pcls[k] < C, MC_ERR_INVALID, "prediction class index out of range");
-        MC_REQUIRE(t.pvert[k] > 0 && t.pvoid[k] >= 0 && t.pvoid[k] <= t.pvert[k], MC_ERR_INVALID, "bad prediction counts");
-        MC_REQUIRE(!std::isnan(t.pscore[k]), MC_ERR_INVALID, "prediction score is NaN");
-    }
-    std::vector<int64_t> gt_poff(static_cast<size_t>(G) + 1, 0);
-    for (int64_t i = 0; i < NP; i++) {
-        const int p = t.ppred[i], g = t.pgt[i];
-        MC_REQUIRE(p >= 0 && p < K && g >= 0 && g < G, MC_ERR_INVALID, "pair index out of range");
-        MC_REQUIRE(t.gcls[g] == t.pcls[p], MC_ERR_INVALID, "pair across classes");
-        MC_REQUIRE(t.pint[i] > 0 && t.pint[i] <= t.gvert[g] && t.pint[i] <= t.pvert[p], MC_ERR_INVALID,
-                   "bad intersection");
-        gt_poff[g + 1]++;
-    }
-    for (int g = 0; g < G; g++) gt_poff[g + 1] += gt_poff[g];
-    // class slots: the classes with an instance or a prediction in this scan
-    std::vector<int> slot(C, -1), g0(C, 0), g1(C, 0), npred(C, 0);
-    std::vector<int64_t> nfilt(C, 0);
-    for (int g = 0; g < G; g++) {
-        const int c = t.gcls[g];
-        if (g1[c] == 0 && (g == 0 || t.gcls[g - 1] != c)) g0[c] = g;
-        g1[c] = g + 1;
-        if (t.gid[g] >= 1000 && t.gvert[g] >= ev.min_region) nfilt[c]++;
-    }
-    for (int k = 0; k < K; k++) npred[t.pcls[k]]++;
-    int A = 0;
-    std::vector<int> cls_of;
-    for (int c = 0; c < C; c++)
-        if (g1[c] > g0[c] || npred[c]) {
-            slot[c] = A++;
-            cls_of.push_back(c);
-        }
-    // the words of EvScanDev
-    const size_t words = 2 * static_cast<size_t>(G) + 4 * static_cast<size_t>(K) + 3 * static_cast<size_t>(NP) + 7 * static_cast<size_t>(A);
-    std::vector<int64_t> W(words + 1, 0);
-    int64_t *gvert = W.data(), *gid = gvert + G, *pvert = gid + G, *pvoid = pvert + K, *pslot = pvoid + K;
-    double *pscore = reinterpret_cast<double *>(pslot + K);
-    int64_t *q_gt = pslot + 2 * K, *q_pred = q_gt + NP, *q_int = q_pred + NP;
-    int64_t *s_p0 = q_int + NP, *s_p1 = s_p0 + A, *s_nfilt = s_p1 + A, *s_npred = s_nfilt + A, *s_cls = s_npred + A,
-            *s_exoff = s_cls + A, *s_cap = s_exoff + A;
-    for (int g = 0; g < G; g++) {
-        gvert[g] = t.gvert[g];
-        gid[g] = t.gid[g];
-    }
-    for (int k = 0; k < K; k++) {
-        pvert[k] = t.pvert[k];
-        pvoid[k] = t.pvoid[k];
-        pslot[k] = slot[t.pcls[k]];
-        pscore[k] = t.pscore[k];
-    }
-    {
-        std::vector<int64_t> at(gt_poff.begin(), gt_poff.end() - 1);  // stable: a ground truth keeps the list's order
-        for (int64_t i = 0; i < NP; i++) {
-            const int64_t j = at[t.pgt[i]]++;
-            q_gt[j] = t.pgt[i];
-            q_pred[j] = t.ppred[i];
-            q_int[j] = t.pint[i];
-        }
-    }
-    int64_t total = 0;
-    for (int a = 0; a < A; a++) {
-        const int c = cls_of[a];
-        const bool has = g1[c] > g0[c];
-        s_p0[a] = has ? gt_poff[g0[c]] : 0;
-        s_p1[a] = has ? gt_poff[g1[c]] : 0;
-        s_nfilt[a] = nfilt[c];
-        s_npred[a] = npred[c];
-        s_cls[a] = c;
-        s_cap[a] = (s_p1[a] - s_p0[a]) + npred[c];
-        s_exoff[a] = total;
-        total += s_cap[a] * O;
-    }
-    const int U = A * O;
-    MC_REQUIRE(ev.ex_used + total < (int64_t(1) << 31) && static_cast<int64_t>(ev.units) + U < (int64_t(1) << 31),
-               MC_ERR_UNSUPPORTED, "more than 2^31 examples");
+    std::vector<int64_t> gt_poff;
+    ev_require(mc::ev_check_tables(t, ev.C, gt_poff), MC_ERR_INVALID);
+    const mc::EvScanPlan p = mc::ev_plan_scan(t, gt_poff, ev.C, ev.O, ev.min_region);
+    ev_require(mc::ev_check_append(ev.ex_used, ev.units, static_cast<unsigned long long>(p.total), p.U), MC_ERR_UNSUPPORTED);
     // ---- from here on the accumulation changes ----
-    ev_grow(ev.d_ex_key, ev.ex_used * 8, (ev.ex_used + total) * 8 + 8, s);
-    ev_grow(ev.d_ex_true, ev.ex_used, ev.ex_used + total + 8, s);
-    ev_grow(ev.d_unit_cell, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
-    ev_grow(ev.d_unit_cnt, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
-    ev_grow(ev.d_unit_off, static_cast<size_t>(ev.units) * 8, static_cast<size_t>(ev.units + U) * 8 + 8, s);
-    if (A) {
-        ev.d_words.reserve(words * 8 + 8);
-        MC_HIP(hipMemcpyAsync(ev.d_words.ptr, W.data(), words * 8, hipMemcpyHostToDevice, s));
-        const size_t b_q = static_cast<size_t>(NP) * 4, b_f = static_cast<size_t>(K) * 4, b_i = static_cast<size_t>(K) * 8,
-                     b_v = static_cast<size_t>(O) * K;
-        const size_t o_i = 0, o_q = o_i + b_i, o_f = o_q + ((b_q + 7) & ~size_t(7)), o_v = o_f + ((b_f + 7) & ~size_t(7));
-        ev.d_tmp.reserve(o_v + b_v + 8);
-        MC_HIP(hipMemsetAsync(ev.d_tmp.ptr, 0, o_v + b_v + 8, s));
-        const int64_t *D = ev.d_words.as<int64_t>();
-        char *T = ev.d_tmp.as<char>();
-        mc::EvScanDev d{};
-        d.G = G, d.K = K, d.NP = static_cast<int>(NP), d.A = A, d.O = O;
-        d.min_region = ev.min_region;
-        d.gvert = D, d.gid = D + G, d.pvert = D + 2 * G, d.pvoid = d.pvert + K, d.pslot = d.pvoid + K;
-        d.pscore = reinterpret_cast<const double *>(d.pslot + K);
-        d.q_gt = d.pslot + 2 * K, d.q_pred = d.q_gt + NP, d.q_int = d.q_pred + NP;
-        d.s_p0 = d.q_int + NP, d.s_p1 = d.s_p0 + A, d.s_nfilt = d.s_p1 + A, d.s_npred = d.s_nfilt + A, d.s_cls = d.s_npred + A;
-        d.s_exoff = d.s_cls + A, d.s_cap = d.s_exoff + A;
-        d.overlaps = ev.d_overlaps.as<double>();
-        d.ign = reinterpret_cast<unsigned long long *>(T + o_i);
-        d.qmask = reinterpret_cast<unsigned *>(T + o_q);
-        d.found = reinterpret_cast<unsigned *>(T + o_f);
-        d.visited = reinterpret_cast<unsigned char *>(T + o_v);
-        d.ex_base = ev.ex_used, d.unit_base = ev.units;
-        d.ex_key = ev.d_ex_key.as<unsigned long long>(), d.ex_true = ev.d_ex_true.as<unsigned char>();
-        d.unit_cell = ev.d_unit_cell.as<int>(), d.unit_cnt = ev.d_unit_cnt.as<int>(), d.unit_off = ev.d_unit_off.as<int64_t>();
-        d.cell_hardfn = ev.d_hardfn.as<unsigned long long>(), d.cell_flags = ev.d_flags.as<unsigned>();
-        TimedScope ts(ctx->timer, s, "ev_greedy");
-        if (NP) hipLaunchKernelGGL(mc::k_ev_qual, grid_for(NP), dim3(256), 0, s, d);
-        hipLaunchKernelGGL(mc::k_ev_greedy, dim3(ceil_div(U, 4)), dim3(256), 0, s, d);
-        if (K) hipLaunchKernelGGL(mc::k_ev_fp, grid_for(static_cast<int64_t>(K) * O), dim3(256), 0, s, d);
-        MC_HIP(hipGetLastError());
-    }
+    ev_reserve_append(ev, p.total, p.U, s);
+    if (p.A) ev_greedy_pass(ctx, t, p);
     MC_HIP(hipStreamSynchronize(s));  // the upload reads this call's host words
     ctx->timer.collect();
-    ev.ex_used += total;
-    ev.units += U;
+    ev.ex_used += p.total;
+    ev.units += p.U;
     ev.last = std::move(t);
     ev.have_last = true;
     ev.ap_valid = false;
     ev.runs_valid = false;
 }
 
-// the device half of mc_ev_add_scan*: every pointer is a device pointer
-void ev_scan_device(mc_ctx *ctx, int64_t P, const int *gt, int K, const int64_t *off, int64_t npts, const int *pts,
-                    const int *pcls, const double *pscore)
+// ---- the device half of mc_ev_add_scan*: every pointer is a device pointer -----------------------
+struct EvScanIn {
+    int64_t P;  // points, with their ground-truth ids
+    const int *gt;
+    int K;  // predictions as point lists (CSR, npts entries), classes and scores (either may be null)
+    const int64_t *off;
+    int64_t npts;
+    const int *pts, *pcls;
+    const double *pscore;
+};
+
+struct EvScanScratch {  // the pieces of d_pk (per prediction: keep, class, pairs, kept-before, pairs-before, vert, void) and d_class
+    int *keep, *pcls, *npair, *kept, *pbase;
+    int64_t *pvert, *pvoid;
+    int *class_cnt, *class_first, *class_off;
+};
+
+// the inputs' ranges on the device; returns R, one more than the largest ground-truth id
+int ev_scan_validate(mc_ctx *ctx, const EvScanIn &in)
 {
     EvState &ev = ctx->ev;
     hipStream_t s = ctx->stream;
-    const int base = ev.class_ids[0] * 1000;
     ev.d_info.reserve(64);
     MC_HIP(hipMemsetAsync(ev.d_info.ptr, 0, 64, s));
-    int info[4] = {0, 0, 0, 0};
+    int info[2] = {0, 0};
     {
         TimedScope ts(ctx->timer, s, "ev_scan");
-        hipLaunchKernelGGL(mc::k_ev_validate, grid_for(std::max<int64_t>(std::max(P, npts), K + 1)), dim3(256), 0, s, P, gt, K,
-                           off, npts, pts, ev.no_class ? 1 : 0, base, ev.d_info.as<int>());
+        hipLaunchKernelGGL(mc::k_ev_validate, grid_for(std::max<int64_t>(std::max(in.P, in.npts), in.K + 1)), dim3(256), 0, s,
+                           in.P, in.gt, in.K, in.off, in.npts, in.pts, ev.no_class ? 1 : 0, ev.class_ids[0] * 1000,
+                           ev.d_info.as<int>());
         MC_HIP(hipGetLastError());
     }
-    MC_HIP(hipMemcpyAsync(info, ev.d_info.ptr, 8, hipMemcpyDeviceToHost, s));
-    MC_HIP(hipStreamSynchronize(s));
+    fetch(ctx, info, ev.d_info.ptr, 8);
     MC_REQUIRE(!(info[0] & 1), MC_ERR_INVALID, "negative ground-truth id");
     MC_REQUIRE(!(info[0] & 4), MC_ERR_INVALID, "prediction offsets must start at 0, ascend and end at num_pred_pts");
     MC_REQUIRE(!(info[0] & 2), MC_ERR_INVALID, "prediction point id out of range");
-    const int R = info[1] + 1, C = ev.C;
-    const size_t gcap = static_cast<size_t>(std::min<int64_t>(R, P)) + 1;
+    return info[1] + 1;
+}
+
+// the scan's device arrays, sized by their bounds (R ids, P points, K predictions, npts pairs)
+EvScanScratch ev_scan_carve(EvState &ev, const EvScanIn &in, int R)
+{
+    const int C = ev.C, K = in.K;
+    const size_t gcap = static_cast<size_t>(std::min<int64_t>(R, in.P)) + 1;
     ev.d_cnt.reserve(static_cast<size_t>(R) * 4);
     ev.d_inst.reserve(static_cast<size_t>(R) * 4);
     ev.d_tmp_id.reserve(gcap * 4);
@@ -192,69 +158,79 @@ void ev_scan_device(mc_ctx *ctx, int64_t P, const int *gt, int K, const int64_t 
     ev.d_gcls.reserve(gcap * 4);
     ev.d_gid.reserve(gcap * 4);
     ev.d_gvert.reserve(gcap * 8);
-    ev.d_pinst.reserve(static_cast<size_t>(P) * 4 + 8);
-    // per prediction: keep, class, pairs, kept-before, pairs-before (int), vert, void (int64)
+    ev.d_pinst.reserve(static_cast<size_t>(in.P) * 4 + 8);
     const size_t k8 = (static_cast<size_t>(K) * 4 + 7) & ~size_t(7);
     ev.d_pk.reserve(5 * k8 + 2 * static_cast<size_t>(K) * 8 + 8);
-    ev.d_pair_gt.reserve(static_cast<size_t>(npts) * 4 + 8);
-    ev.d_pair_int.reserve(static_cast<size_t>(npts) * 8 + 8);
+    ev.d_pair_gt.reserve(static_cast<size_t>(in.npts) * 4 + 8);
+    ev.d_pair_int.reserve(static_cast<size_t>(in.npts) * 8 + 8);
+    // the compact tables as one run of words
+    ev.d_out.reserve((3 * gcap + 4 * static_cast<size_t>(K) + 3 * static_cast<size_t>(in.npts) + 1) * 8);
     char *pk = ev.d_pk.as<char>();
-    int *d_keep = reinterpret_cast<int *>(pk), *d_pcls = reinterpret_cast<int *>(pk + k8),
-        *d_npair = reinterpret_cast<int *>(pk + 2 * k8), *d_kept = reinterpret_cast<int *>(pk + 3 * k8),
-        *d_pbase = reinterpret_cast<int *>(pk + 4 * k8);
-    int64_t *d_pvert = reinterpret_cast<int64_t *>(pk + 5 * k8), *d_pvoid = d_pvert + K;
-    int *class_cnt = ev.d_class.as<int>(), *class_first = class_cnt + C, *class_off = class_first + C;
-    // the compact tables as one run of words, sized by their bounds (instances, K predictions, npts pairs)
-    ev.d_out.reserve((3 * gcap + 4 * static_cast<size_t>(K) + 3 * static_cast<size_t>(npts) + 1) * 8);
+    EvScanScratch t;
+    t.keep = reinterpret_cast<int *>(pk), t.pcls = reinterpret_cast<int *>(pk + k8);
+    t.npair = reinterpret_cast<int *>(pk + 2 * k8), t.kept = reinterpret_cast<int *>(pk + 3 * k8);
+    t.pbase = reinterpret_cast<int *>(pk + 4 * k8);
+    t.pvert = reinterpret_cast<int64_t *>(pk + 5 * k8), t.pvoid = t.pvert + K;
+    t.class_cnt = ev.d_class.as<int>(), t.class_first = t.class_cnt + C, t.class_off = t.class_first + C;
+    return t;
+}
+
+// instances, kept predictions and their pairs into d_out, the three sizes into d_info + 4 (launches only)
+void ev_scan_launch(mc_ctx *ctx, const EvScanIn &in, int R, const EvScanScratch &t)
+{
+    EvState &ev = ctx->ev;
+    hipStream_t s = ctx->stream;
+    const int C = ev.C, K = in.K, nc = ev.no_class ? 1 : 0, base = ev.class_ids[0] * 1000;
+    const int64_t P = in.P;
+    int *sizes = ev.d_info.as<int>() + 4;
     MC_HIP(hipMemsetAsync(ev.d_cnt.ptr, 0, static_cast<size_t>(R) * 4, s));
     MC_HIP(hipMemsetAsync(ev.d_inst.ptr, 0xff, static_cast<size_t>(R) * 4, s));
-    MC_HIP(hipMemsetAsync(class_cnt, 0, static_cast<size_t>(C) * 4, s));
-    MC_HIP(hipMemsetAsync(class_first, 0x7f, static_cast<size_t>(C) * 4, s));
-    {
-        TimedScope ts(ctx->timer, s, "ev_scan");
-        if (P && R <= mc::kEvCountLds)
-            hipLaunchKernelGGL(mc::k_ev_gt_count_lds, grid_for(P, 2048, 256), dim3(256), 0, s, P, gt, ev.no_class ? 1 : 0, base, R,
-                               ev.d_cnt.as<int>());
-        else if (P)
-            hipLaunchKernelGGL(mc::k_ev_gt_count, grid_for(P), dim3(256), 0, s, P, gt, ev.no_class ? 1 : 0, base,
-                               ev.d_cnt.as<int>());
-        hipLaunchKernelGGL(mc::k_ev_gt_table, dim3(1), dim3(1024), 0, s, R, ev.d_cnt.as<int>(), ev.d_lab2cls.as<int>(), ev.nlab,
-                           C, ev.d_tmp_id.as<int>(), class_cnt, class_first, class_off, ev.d_gcls.as<int>(),
-                           ev.d_gid.as<int>(), ev.d_gvert.as<int64_t>(), ev.d_inst.as<int>(), ev.d_info.as<int>() + 4);
-        if (P)
-            hipLaunchKernelGGL(mc::k_ev_point_inst, grid_for(P), dim3(256), 0, s, P, gt, ev.no_class ? 1 : 0, base,
-                               ev.d_lab2cls.as<int>(), ev.nlab, ev.d_inst.as<int>(), ev.d_pinst.as<int>());
-        if (K)
-            hipLaunchKernelGGL(mc::k_ev_inter, dim3(std::min(K, 8192)), dim3(256), 0, s, K, off, pts, pcls, ev.no_class ? 1 : 0,
-                               ev.d_lab2cls.as<int>(), ev.nlab, static_cast<int>(std::min<int64_t>(ev.min_region, INT32_MAX)),
-                               ev.d_pinst.as<int>(), class_off, d_keep, d_pcls, d_pvert, d_pvoid, d_npair,
-                               ev.d_pair_gt.as<int>(), ev.d_pair_int.as<int64_t>());
-        hipLaunchKernelGGL(mc::k_ev_pred_scan, dim3(1), dim3(1024), 0, s, K, d_keep, d_npair, d_kept, d_pbase,
-                           ev.d_info.as<int>() + 4);
-        hipLaunchKernelGGL(mc::k_ev_compact, dim3(std::max(1, std::min(K, 8192))), dim3(256), 0, s, K, off, d_keep, d_kept, d_pbase,
-                           d_npair, d_pcls, d_pvert, d_pvoid, pscore, ev.d_pair_gt.as<int>(), ev.d_pair_int.as<int64_t>(),
-                           ev.d_gcls.as<int>(), ev.d_gid.as<int>(), ev.d_gvert.as<int64_t>(), ev.d_info.as<int>() + 4,
-                           ev.d_out.as<int64_t>());
-        MC_HIP(hipGetLastError());
-    }
-    MC_HIP(hipMemcpyAsync(info, ev.d_info.as<int>() + 4, 12, hipMemcpyDeviceToHost, s));
-    MC_HIP(hipStreamSynchronize(s));
-    const int G = info[0], Kk = info[1], NP = info[2];
-    const size_t words = 3 * static_cast<size_t>(G) + 4 * static_cast<size_t>(Kk) + 3 * static_cast<size_t>(NP);
+    MC_HIP(hipMemsetAsync(t.class_cnt, 0, static_cast<size_t>(C) * 4, s));
+    MC_HIP(hipMemsetAsync(t.class_first, 0x7f, static_cast<size_t>(C) * 4, s));
+    TimedScope ts(ctx->timer, s, "ev_scan");
+    if (P && R <= mc::kEvCountLds)
+        hipLaunchKernelGGL(mc::k_ev_gt_count_lds, grid_for(P, 2048, 256), dim3(256), 0, s, P, in.gt, nc, base, R,
+                           ev.d_cnt.as<int>());
+    else if (P)
+        hipLaunchKernelGGL(mc::k_ev_gt_count, grid_for(P), dim3(256), 0, s, P, in.gt, nc, base, ev.d_cnt.as<int>());
+    hipLaunchKernelGGL(mc::k_ev_gt_table, dim3(1), dim3(1024), 0, s, R, ev.d_cnt.as<int>(), ev.d_lab2cls.as<int>(), ev.nlab, C,
+                       ev.d_tmp_id.as<int>(), t.class_cnt, t.class_first, t.class_off, ev.d_gcls.as<int>(), ev.d_gid.as<int>(),
+                       ev.d_gvert.as<int64_t>(), ev.d_inst.as<int>(), sizes);
+    if (P)
+        hipLaunchKernelGGL(mc::k_ev_point_inst, grid_for(P), dim3(256), 0, s, P, in.gt, nc, base, ev.d_lab2cls.as<int>(),
+                           ev.nlab, ev.d_inst.as<int>(), ev.d_pinst.as<int>());
+    if (K)
+        hipLaunchKernelGGL(mc::k_ev_inter, dim3(std::min(K, 8192)), dim3(256), 0, s, K, in.off, in.pts, in.pcls, nc,
+                           ev.d_lab2cls.as<int>(), ev.nlab, static_cast<int>(std::min<int64_t>(ev.min_region, INT32_MAX)),
+                           ev.d_pinst.as<int>(), t.class_off, t.keep, t.pcls, t.pvert, t.pvoid, t.npair,
+                           ev.d_pair_gt.as<int>(), ev.d_pair_int.as<int64_t>());
+    hipLaunchKernelGGL(mc::k_ev_pred_scan, dim3(1), dim3(1024), 0, s, K, t.keep, t.npair, t.kept, t.pbase, sizes);
+    hipLaunchKernelGGL(mc::k_ev_compact, dim3(std::max(1, std::min(K, 8192))), dim3(256), 0, s, K, in.off, t.keep, t.kept,
+                       t.pbase, t.npair, t.pcls, t.pvert, t.pvoid, in.pscore, ev.d_pair_gt.as<int>(),
+                       ev.d_pair_int.as<int64_t>(), ev.d_gcls.as<int>(), ev.d_gid.as<int>(), ev.d_gvert.as<int64_t>(), sizes,
+                       ev.d_out.as<int64_t>());
+    MC_HIP(hipGetLastError());
+}
+
+// the sizes, then the compact tables, to the host
+EvTables ev_scan_fetch(mc_ctx *ctx)
+{
+    EvState &ev = ctx->ev;
+    int n[3] = {0, 0, 0};  // instances, kept predictions, pairs
+    fetch(ctx, n, ev.d_info.as<int>() + 4, 12);
+    const size_t words = mc::ev_compact_words(n[0], n[1], n[2]);
     ev.h_out.resize(words + 1);
-    if (words) MC_HIP(hipMemcpyAsync(ev.h_out.data(), ev.d_out.ptr, words * 8, hipMemcpyDeviceToHost, s));
-    MC_HIP(hipStreamSynchronize(s));
+    fetch(ctx, ev.h_out.data(), ev.d_out.ptr, words * 8);
     ctx->timer.collect();
-    const int64_t *w = ev.h_out.data();
-    EvTables t;
-    t.gcls.assign(w, w + G), t.gid.assign(w + G, w + 2 * G), t.gvert.assign(w + 2 * G, w + 3 * G);
-    w += 3 * static_cast<size_t>(G);
-    t.pcls.assign(w, w + Kk), t.pvert.assign(w + Kk, w + 2 * Kk), t.pvoid.assign(w + 2 * Kk, w + 3 * Kk);
-    t.pscore.resize(Kk);
-    if (Kk) std::memcpy(t.pscore.data(), w + 3 * static_cast<size_t>(Kk), static_cast<size_t>(Kk) * 8);
-    w += 4 * static_cast<size_t>(Kk);
-    t.ppred.assign(w, w + NP), t.pgt.assign(w + NP, w + 2 * NP), t.pint.assign(w + 2 * NP, w + 3 * NP);
-    ev_commit(ctx, std::move(t));
+    return mc::ev_unpack_tables(ev.h_out.data(), n[0], n[1], n[2]);
+}
+
+void ev_scan_device(mc_ctx *ctx, const EvScanIn &in)
+{
+    const int R = ev_scan_validate(ctx, in);
+    const EvScanScratch t = ev_scan_carve(ctx->ev, in, R);
+    ev_scan_launch(ctx, in, R, t);
+    ev_commit(ctx, ev_scan_fetch(ctx));
 }
 
 // every unit's examples into its cell's segment of d_key / d_true (launches only); returns cell_off [NC + 1]
@@ -313,29 +289,6 @@ void ev_compute(mc_ctx *ctx, int curve_cell, double *cv_score, int64_t *cv_tp, i
 }
 
 // ---- the accumulation as a state buffer (include/mcgraph.h, mc_ev_state_*) -----------------------
-constexpr int64_t kEvStateWord = (int64_t(1) << 32) | 0x5645434d;  // version 1, "MCEV"
-constexpr size_t kEvStateHeader = 48;
-
-struct EvLayout {  // byte offsets of the sections
-    size_t ids, ov, roff, hf, fl, key, nt, nf, bytes;
-};
-
-EvLayout ev_layout(int C, int O, int64_t R)
-{
-    auto up = [](size_t b) { return (b + 7) & ~size_t(7); };
-    const size_t NC = static_cast<size_t>(C) * O, r = static_cast<size_t>(R);
-    EvLayout L;
-    L.ids = kEvStateHeader;
-    L.ov = L.ids + up(4 * static_cast<size_t>(C));
-    L.roff = L.ov + 8 * static_cast<size_t>(O);
-    L.hf = L.roff + 8 * (NC + 1);
-    L.fl = L.hf + 8 * NC;
-    L.key = L.fl + up(4 * NC);
-    L.nt = L.key + 8 * r;
-    L.nf = L.nt + up(4 * r);
-    L.bytes = L.nf + up(4 * r);
-    return L;
-}
 
 // the state buffer of the accumulation in d_state, kept until the accumulation changes
 void ev_runs(mc_ctx *ctx)
@@ -360,9 +313,9 @@ void ev_runs(mc_ctx *ctx)
     MC_HIP(hipMemcpyAsync(&tot[1], cell_off + NC, 4, hipMemcpyDeviceToHost, s));
     MC_HIP(hipStreamSynchronize(s));
     const int64_t R = tot[0];
-    const EvLayout L = ev_layout(C, O, R);
+    const mc::EvLayout L = mc::ev_layout(C, O, R);
     std::vector<int64_t> head(L.roff / 8, 0);
-    head[0] = kEvStateWord, head[1] = C, head[2] = O, head[3] = ev.min_region, head[4] = ev.no_class ? 1 : 0, head[5] = R;
+    head[0] = mc::kEvStateWord, head[1] = C, head[2] = O, head[3] = ev.min_region, head[4] = ev.no_class ? 1 : 0, head[5] = R;
     char *hb = reinterpret_cast<char *>(head.data());
     std::memcpy(hb + L.ids, ev.class_ids.data(), static_cast<size_t>(C) * 4);
     std::memcpy(hb + L.ov, ev.overlaps.data(), static_cast<size_t>(O) * 8);
@@ -386,61 +339,70 @@ void ev_runs(mc_ctx *ctx)
     ev.runs_valid = true;
 }
 
-void ev_merge(mc_ctx *ctx, const void *buf, int64_t bytes, bool on_device)
+// ---- mc_ev_state_merge ---------------------------------------------------------------------------
+struct EvMergeSrc {
+    const char *buf;
+    int64_t bytes;
+    bool on_device;
+};
+
+// The header, then (once it is known to fit) the sections up to the keys, to the host and through the checks
+// of mc_ap_plan.hpp: two fetches for a device buffer.  Returns the layout; cells: the cells with runs.
+mc::EvLayout ev_merge_parse(mc_ctx *ctx, const EvMergeSrc &m, std::vector<int> &cells)
+{
+    const EvState &ev = ctx->ev;
+    auto take = [&](void *dst, size_t at, size_t n) {  // a part of the buffer to the host
+        if (m.on_device) fetch(ctx, dst, m.buf + at, n);
+        else std::memcpy(dst, m.buf + at, n);
+    };
+    const bool has_header = m.buf && m.bytes >= static_cast<int64_t>(mc::kEvStateHeader);
+    MC_REQUIRE(!has_header || !m.on_device || (reinterpret_cast<uintptr_t>(m.buf) & 7) == 0, MC_ERR_INVALID,
+               "state buffer must be 8-byte aligned");
+    int64_t hdr[6], R = 0;
+    if (has_header) take(hdr, 0, mc::kEvStateHeader);
+    ev_require(mc::ev_check_state_header(has_header ? hdr : nullptr, m.bytes, ev.C, ev.O, ev.min_region, ev.no_class, R),
+               MC_ERR_INVALID);
+    const mc::EvLayout L = mc::ev_layout(ev.C, ev.O, R);
+    std::vector<int64_t> mid((L.key - L.ids) / 8);
+    take(mid.data(), L.ids, L.key - L.ids);
+    ev_require(mc::ev_check_state_sections(mid.data(), L, ev.class_ids, ev.overlaps, cells), MC_ERR_INVALID);
+    return L;
+}
+
+// the buffer's sections on the device (a host buffer is uploaded to d_merge)
+struct EvStateDev {
+    const int64_t *roff, *hf;
+    const unsigned *fl, *nt, *nf;
+    const unsigned long long *key;
+};
+
+EvStateDev ev_merge_sections(mc_ctx *ctx, const EvMergeSrc &m, const mc::EvLayout &L)
+{
+    EvState &ev = ctx->ev;
+    const char *D = m.buf;
+    if (!m.on_device) {
+        ev.d_merge.reserve(L.bytes);
+        MC_HIP(hipMemcpyAsync(ev.d_merge.ptr, m.buf, L.bytes, hipMemcpyHostToDevice, ctx->stream));
+        D = ev.d_merge.as<char>();
+    }
+    EvStateDev d;
+    d.roff = reinterpret_cast<const int64_t *>(D + L.roff), d.hf = reinterpret_cast<const int64_t *>(D + L.hf);
+    d.fl = reinterpret_cast<const unsigned *>(D + L.fl);
+    d.key = reinterpret_cast<const unsigned long long *>(D + L.key);
+    d.nt = reinterpret_cast<const unsigned *>(D + L.nt), d.nf = reinterpret_cast<const unsigned *>(D + L.nf);
+    return d;
+}
+
+// the run checks behind one flag word; returns the examples of all runs
+unsigned long long ev_merge_check_runs(mc_ctx *ctx, const EvStateDev &d, int64_t R)
 {
     EvState &ev = ctx->ev;
     hipStream_t s = ctx->stream;
-    const int C = ev.C, O = ev.O, NC = C * O;
-    MC_REQUIRE(buf && bytes >= static_cast<int64_t>(kEvStateHeader), MC_ERR_INVALID, "state buffer is truncated");
-    MC_REQUIRE(!on_device || (reinterpret_cast<uintptr_t>(buf) & 7) == 0, MC_ERR_INVALID, "state buffer must be 8-byte aligned");
-    const char *src = static_cast<const char *>(buf);
-    auto take = [&](void *dst, size_t at, size_t n) {  // a part of the buffer to the host
-        if (on_device) fetch(ctx, dst, src + at, n);
-        else std::memcpy(dst, src + at, n);
-    };
-    int64_t hdr[6];
-    take(hdr, 0, kEvStateHeader);
-    MC_REQUIRE(hdr[0] == kEvStateWord, MC_ERR_INVALID, "not a state buffer of this version");
-    MC_REQUIRE(hdr[1] == C && hdr[2] == O && hdr[3] == ev.min_region && hdr[4] == (ev.no_class ? 1 : 0), MC_ERR_INVALID,
-               "state buffer of another configuration");
-    const int64_t R = hdr[5];
-    MC_REQUIRE(R >= 0 && R < (int64_t(1) << 31), MC_ERR_INVALID, "bad run count");
-    const EvLayout L = ev_layout(C, O, R);
-    MC_REQUIRE(static_cast<int64_t>(L.bytes) <= bytes, MC_ERR_INVALID, "state buffer is truncated");
-    // configuration and per-cell sections on the host
-    std::vector<int64_t> mid((L.key - L.ids) / 8);
-    take(mid.data(), L.ids, L.key - L.ids);
-    const char *mb = reinterpret_cast<const char *>(mid.data()) - L.ids;
-    MC_REQUIRE(std::memcmp(mb + L.ids, ev.class_ids.data(), static_cast<size_t>(C) * 4) == 0 &&
-                   std::memcmp(mb + L.ov, ev.overlaps.data(), static_cast<size_t>(O) * 8) == 0,
-               MC_ERR_INVALID, "state buffer of another configuration");
-    const int64_t *roff = reinterpret_cast<const int64_t *>(mb + L.roff), *hf = reinterpret_cast<const int64_t *>(mb + L.hf);
-    const uint32_t *fl = reinterpret_cast<const uint32_t *>(mb + L.fl);
-    MC_REQUIRE(roff[0] == 0 && roff[NC] == R, MC_ERR_INVALID, "run offsets must ascend from 0 to the run count");
-    std::vector<int> cells;
-    for (int c = 0; c < NC; c++) {
-        MC_REQUIRE(roff[c + 1] >= roff[c], MC_ERR_INVALID, "run offsets must ascend from 0 to the run count");
-        MC_REQUIRE(hf[c] >= 0, MC_ERR_INVALID, "negative hard false negative count");
-        MC_REQUIRE(fl[c] <= 3u, MC_ERR_INVALID, "unknown flag bits");
-        if (roff[c + 1] > roff[c]) cells.push_back(c);
-    }
-    const int U = static_cast<int>(cells.size());
-    const char *D = src;
-    if (!on_device) {
-        ev.d_merge.reserve(L.bytes);
-        MC_HIP(hipMemcpyAsync(ev.d_merge.ptr, src, L.bytes, hipMemcpyHostToDevice, s));
-        D = ev.d_merge.as<char>();
-    }
-    const int64_t *d_roff = reinterpret_cast<const int64_t *>(D + L.roff), *d_hf = reinterpret_cast<const int64_t *>(D + L.hf);
-    const unsigned *d_fl = reinterpret_cast<const unsigned *>(D + L.fl);
-    const unsigned long long *d_key = reinterpret_cast<const unsigned long long *>(D + L.key);
-    const unsigned *d_nt = reinterpret_cast<const unsigned *>(D + L.nt), *d_nf = reinterpret_cast<const unsigned *>(D + L.nf);
-    // the run checks behind one flag word, and the examples of all runs
     ev.d_info.reserve(64);
     MC_HIP(hipMemsetAsync(ev.d_info.ptr, 0, 16, s));
     if (R) {
         TimedScope ts(ctx->timer, s, "ev_merge");
-        hipLaunchKernelGGL(mc::k_ev_state_check, grid_for(R), dim3(256), 0, s, NC, R, d_roff, d_key, d_nt, d_nf,
+        hipLaunchKernelGGL(mc::k_ev_state_check, grid_for(R), dim3(256), 0, s, ev.C * ev.O, R, d.roff, d.key, d.nt, d.nf,
                            ev.d_info.as<int>(), reinterpret_cast<unsigned long long *>(ev.d_info.as<char>() + 8));
         MC_HIP(hipGetLastError());
     }
@@ -450,34 +412,46 @@ void ev_merge(mc_ctx *ctx, const void *buf, int64_t bytes, bool on_device)
     MC_REQUIRE(!(bad & 1), MC_ERR_INVALID, "a run without examples");
     MC_REQUIRE(!(bad & 2), MC_ERR_INVALID, "a key that is no score (NaN)");
     MC_REQUIRE(!(bad & 4), MC_ERR_INVALID, "keys must ascend strictly within a cell");
-    const unsigned long long total = chk[1];
-    MC_REQUIRE(total < (1ull << 31) && ev.ex_used + static_cast<int64_t>(total) < (int64_t(1) << 31) &&
-                   static_cast<int64_t>(ev.units) + U < (int64_t(1) << 31),
-               MC_ERR_UNSUPPORTED, "more than 2^31 examples");
-    // ---- from here on the accumulation changes ----
-    const int64_t add = static_cast<int64_t>(total);
-    ev_grow(ev.d_ex_key, ev.ex_used * 8, (ev.ex_used + add) * 8 + 8, s);
-    ev_grow(ev.d_ex_true, ev.ex_used, ev.ex_used + add + 8, s);
-    ev_grow(ev.d_unit_cell, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
-    ev_grow(ev.d_unit_cnt, static_cast<size_t>(ev.units) * 4, static_cast<size_t>(ev.units + U) * 4 + 8, s);
-    ev_grow(ev.d_unit_off, static_cast<size_t>(ev.units) * 8, static_cast<size_t>(ev.units + U) * 8 + 8, s);
+    return chk[1];
+}
+
+// the runs' examples behind the accumulation's, one unit per cell with runs (launches only)
+void ev_merge_expand(mc_ctx *ctx, const EvStateDev &d, int64_t R, int64_t add, const std::vector<int> &cells)
+{
+    EvState &ev = ctx->ev;
+    hipStream_t s = ctx->stream;
+    const int NC = ev.C * ev.O, U = static_cast<int>(cells.size());
     ev.d_tmp.reserve(static_cast<size_t>(U) * 4 + 8);
     ev.d_words.reserve((static_cast<size_t>(R) + 1) * 4 + 8);
     if (U) MC_HIP(hipMemcpyAsync(ev.d_tmp.ptr, cells.data(), static_cast<size_t>(U) * 4, hipMemcpyHostToDevice, s));
     int *run_ex = ev.d_words.as<int>();
-    {
-        TimedScope ts(ctx->timer, s, "ev_merge");
-        if (R) {
-            hipLaunchKernelGGL(mc::k_ev_state_scan, dim3(1), dim3(1024), 0, s, static_cast<int>(R), d_nt, d_nf, run_ex);
-            hipLaunchKernelGGL(mc::k_ev_state_expand, grid_for(add), dim3(256), 0, s, static_cast<int>(R), run_ex, d_key, d_nt,
-                               ev.d_ex_key.as<unsigned long long>() + ev.ex_used, ev.d_ex_true.as<unsigned char>() + ev.ex_used);
-        }
-        hipLaunchKernelGGL(mc::k_ev_state_units, grid_for(std::max(NC, U)), dim3(256), 0, s, NC, U, ev.d_tmp.as<int>(), d_roff,
-                           run_ex, d_hf, d_fl, ev.ex_used, ev.d_unit_cell.as<int>() + ev.units, ev.d_unit_cnt.as<int>() + ev.units,
-                           ev.d_unit_off.as<int64_t>() + ev.units, ev.d_hardfn.as<unsigned long long>(),
-                           ev.d_flags.as<unsigned>());
-        MC_HIP(hipGetLastError());
+    TimedScope ts(ctx->timer, s, "ev_merge");
+    if (R) {
+        hipLaunchKernelGGL(mc::k_ev_state_scan, dim3(1), dim3(1024), 0, s, static_cast<int>(R), d.nt, d.nf, run_ex);
+        hipLaunchKernelGGL(mc::k_ev_state_expand, grid_for(add), dim3(256), 0, s, static_cast<int>(R), run_ex, d.key, d.nt,
+                           ev.d_ex_key.as<unsigned long long>() + ev.ex_used, ev.d_ex_true.as<unsigned char>() + ev.ex_used);
     }
+    hipLaunchKernelGGL(mc::k_ev_state_units, grid_for(std::max(NC, U)), dim3(256), 0, s, NC, U, ev.d_tmp.as<int>(), d.roff,
+                       run_ex, d.hf, d.fl, ev.ex_used, ev.d_unit_cell.as<int>() + ev.units, ev.d_unit_cnt.as<int>() + ev.units,
+                       ev.d_unit_off.as<int64_t>() + ev.units, ev.d_hardfn.as<unsigned long long>(), ev.d_flags.as<unsigned>());
+    MC_HIP(hipGetLastError());
+}
+
+void ev_merge(mc_ctx *ctx, const EvMergeSrc &m)
+{
+    EvState &ev = ctx->ev;
+    hipStream_t s = ctx->stream;
+    std::vector<int> cells;
+    const mc::EvLayout L = ev_merge_parse(ctx, m, cells);
+    const int64_t R = static_cast<int64_t>((L.nt - L.key) / 8);
+    const int U = static_cast<int>(cells.size());
+    const EvStateDev d = ev_merge_sections(ctx, m, L);
+    const unsigned long long total = ev_merge_check_runs(ctx, d, R);
+    ev_require(mc::ev_check_append(ev.ex_used, ev.units, total, U), MC_ERR_UNSUPPORTED);
+    // ---- from here on the accumulation changes ----
+    const int64_t add = static_cast<int64_t>(total);
+    ev_reserve_append(ev, add, U, s);
+    ev_merge_expand(ctx, d, R, add, cells);
     MC_HIP(hipStreamSynchronize(s));  // the uploads read this call's host words
     ctx->timer.collect();
     ev.ex_used += add;
@@ -542,7 +516,7 @@ int mc_ev_add_scan(mc_ctx *ctx, int64_t num_points, const int32_t *gt_ids, int32
                    MC_ERR_INVALID, "bad size");
         MC_REQUIRE(pred_off && (num_points == 0 || gt_ids) && (num_pred_pts == 0 || pred_pts), MC_ERR_INVALID, "null argument");
         if (on_device) {
-            ev_scan_device(ctx, num_points, gt_ids, num_pred, pred_off, num_pred_pts, pred_pts, pred_classes, pred_scores);
+            ev_scan_device(ctx, {num_points, gt_ids, num_pred, pred_off, num_pred_pts, pred_pts, pred_classes, pred_scores});
             return;
         }
         hipStream_t s = ctx->stream;
@@ -554,9 +528,9 @@ int mc_ev_add_scan(mc_ctx *ctx, int64_t num_points, const int32_t *gt_ids, int32
             ev.d_in[i].reserve(bytes[i] + 8);
             if (src[i] && bytes[i]) MC_HIP(hipMemcpyAsync(ev.d_in[i].ptr, src[i], bytes[i], hipMemcpyHostToDevice, s));
         }
-        ev_scan_device(ctx, num_points, ev.d_in[0].as<int>(), num_pred, ev.d_in[1].as<int64_t>(), num_pred_pts,
-                       ev.d_in[2].as<int>(), pred_classes ? ev.d_in[3].as<int>() : nullptr,
-                       pred_scores ? ev.d_in[4].as<double>() : nullptr);
+        ev_scan_device(ctx, {num_points, ev.d_in[0].as<int>(), num_pred, ev.d_in[1].as<int64_t>(), num_pred_pts,
+                             ev.d_in[2].as<int>(), pred_classes ? ev.d_in[3].as<int>() : nullptr,
+                             pred_scores ? ev.d_in[4].as<double>() : nullptr});
     });
 }
 
@@ -578,7 +552,7 @@ int mc_ev_add_scan_clustered(mc_ctx *ctx, const int32_t *gt_ids, int on_device)
             if (P) MC_HIP(hipMemcpyAsync(ev.d_in[0].ptr, gt_ids, static_cast<size_t>(P) * 4, hipMemcpyHostToDevice, ctx->stream));
             gt = ev.d_in[0].as<int>();
         }
-        ev_scan_device(ctx, P, gt, nf, pp.d_opoff.as<int64_t>(), np, pp.d_opts.as<int>(), nullptr, nullptr);
+        ev_scan_device(ctx, {P, gt, nf, pp.d_opoff.as<int64_t>(), np, pp.d_opts.as<int>(), nullptr, nullptr});
     });
 }
 
@@ -701,7 +675,7 @@ int mc_ev_state_merge(mc_ctx *ctx, const void *buf, int64_t bytes, int on_device
 {
     return guarded(ctx, [&] {
         MC_REQUIRE(ctx->ev.active, MC_ERR_STATE, "mc_ev_begin first");
-        ev_merge(ctx, buf, bytes, on_device != 0);
+        ev_merge(ctx, {static_cast<const char *>(buf), bytes, on_device != 0});
     });
 }
 

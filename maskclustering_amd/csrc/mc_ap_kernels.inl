@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void k_ev_compact(int K, const int64_t *__rest
 // The scan's tables as 8-byte words (built by the host from the compact tables): per instance
 // vert / id, per prediction vert / void / score / class slot, the pairs in ground-truth order
 // (ascending prediction within an instance), per class slot its pair range, counts and example
-// region.
+// region.  The order of the words has one definition, ev_words() of mc_ap_plan.hpp.
 struct EvScanDev {
     int G, K, NP, A, O;
     int64_t min_region;

@@ -21,6 +21,7 @@
 #include "mc_bp_plan.hpp"
 #include "mc_graph_plan.hpp"
 #include "mc_pp_plan.hpp"
+#include "mc_ap_plan.hpp"
 #include "mc_crop_plan.hpp"
 #include "mc_proj_plan.hpp"
 #include "mc_kernels.inl"
@@ -36,6 +37,7 @@
 #include "mc_setorder.inl"
 
 using mc::DevBuf;
+using mc::EvTables;
 using mc::McError;
 using mc::TimedScope;
 using mc::ceil_div;
@@ -266,6 +268,7 @@ int mc_debug_counters(mc_ctx *ctx, int64_t *out, int32_t n, int reset)
 #include "mc_shard_host.inl"
 #include "mc_bp_host.inl"
 #include "mc_pp_host.inl"
+#include "mc_ap_host.inl"
 #include "mc_crop_host.inl"
 #include "mc_proj_host.inl"
 
@@ -463,5 +466,3 @@ int mc_openvoc_query(mc_ctx *ctx, int32_t num_objects, const int64_t *obj_off, c
 }
 
 }  // extern "C"
-
-#include "mc_ap_host.inl"

@@ -76,13 +76,7 @@ struct BpState {
     std::vector<int64_t> off;
 };
 
-// AP evaluation state of a context (the host code is mc_ap_host.inl)
-struct EvTables {  // one scan's compact tables (include/mcgraph.h, mc_ev_get_scan)
-    std::vector<int32_t> gcls, gid, pcls, ppred, pgt;
-    std::vector<int64_t> gvert, pvert, pvoid, pint;
-    std::vector<double> pscore;
-};
-
+// AP evaluation state of a context (the host code is mc_ap_host.inl; EvTables is mc_ap_plan.hpp's)
 struct EvState {
     bool active = false;
     int C = 0, O = 0, nlab = 0;
@@ -106,11 +100,15 @@ struct EvState {
     // the accumulation as runs (mc_ev_state_*): the state buffer of the last export, kept on the device
     bool runs_valid = false;
     int64_t state_runs = 0, state_examples = 0, state_bytes = 0;
-    DevBuf d_state, d_run, d_merge;
-    // scratch of one mc_ev_add_scan / commit
+    DevBuf d_state, d_run;
+    // scratch of one call, by the step that writes it
+    DevBuf d_in[5];  // mc_ev_add_scan*: the host arguments' device copies
+    DevBuf d_info;   // validate (ev_scan_validate, ev_merge_check_runs): the flag words; the scan's table sizes
+    // the scan tables (ev_scan_carve, ev_scan_launch, ev_scan_fetch): compact tables in d_out, fetched to h_out
+    DevBuf d_cnt, d_inst, d_tmp_id, d_class, d_gcls, d_gid, d_gvert, d_pinst, d_pk, d_pair_gt, d_pair_int, d_out;
     std::vector<int64_t> h_out;
-    DevBuf d_info, d_in[5], d_cnt, d_inst, d_tmp_id, d_class, d_gcls, d_gid, d_gvert, d_pinst, d_pk, d_pair_gt, d_pair_int,
-        d_out, d_words, d_tmp;
+    DevBuf d_words, d_tmp;  // commit (ev_greedy_pass): the word block and the pass's temporaries; the merge's run offsets and cells
+    DevBuf d_merge;         // merge (ev_merge_sections): the device copy of a host state buffer
 };
 
 // CLIP crop preparation (mc_crop_*; the host code is mc_crop_host.inl): the context's pools

@@ -334,3 +334,56 @@ def test_errors():
     for x, y in zip(ctx.ev_ap(), fresh.ev_ap()):
         np.testing.assert_array_equal(x, y)
     check_result(ctx, restated("ca", 2)[0], restated("ca", 2), "after errors")
+
+
+def worked_tables():
+    """The worked scan of scripts/ap_plan_check.cpp: class index 0 has instances 0 and 1 (a group id) and
+    predictions 0 and 1, class index 1 prediction 2 alone, class index 2 instances 2 and 3 (below
+    min_region_size) alone; the four pairs are listed shuffled."""
+    return dict(gt_cls=np.array([0, 0, 2, 2], np.int32), gt_id=np.array([3001, 500, 8002, 8003], np.int32),
+                gt_vert=np.array([300, 200, 150, 60], np.int64), pr_cls=np.array([0, 0, 1], np.int32),
+                pr_vert=np.array([280, 120, 90], np.int64), pr_void=np.array([10, 0, 5], np.int64),
+                pr_score=np.array([0.9, 0.4, 0.7], np.float64), pair_pred=np.array([1, 1, 0, 0], np.int32),
+                pair_gt=np.array([1, 0, 1, 0], np.int32), pair_int=np.array([20, 90, 15, 250], np.int64))
+
+
+def test_rejected_tables_leave_the_accumulation():
+    """The eleven table rules of mc_ev_add_matches, each broken alone on the worked scan: MC_ERR_INVALID with
+    the rule's message, and the table, the stats and the last scan stay bit for bit what they were."""
+    from maskclustering_amd._native import McError
+    good = worked_tables()
+    broken = (("gt_cls", 3, 3, "ascending class"),        # no class index
+              ("gt_cls", 0, 2, "ascending class"),        # descending
+              ("gt_vert", 2, 0, "vert_count"),
+              ("pr_cls", 1, -1, "class index"),
+              ("pr_vert", 0, 0, "prediction counts"),
+              ("pr_void", 2, 91, "prediction counts"),    # more void than vertices
+              ("pr_score", 1, np.nan, "NaN"),
+              ("pair_pred", 0, 3, "pair index"),
+              ("pair_gt", 2, -1, "pair index"),
+              ("pair_gt", 0, 2, "across classes"),        # prediction 1 of class index 0, instance 2 of class index 2
+              ("pair_int", 3, 281, "intersection"))       # above the prediction's 280 vertices
+    ctx = new_ctx()
+    ctx.ev_begin(CLS, None, 100, False)
+    ctx.ev_add_matches(good)
+    ap, stats = ctx.ev_ap()
+    last = ctx.ev_scan()
+    R.assert_tables_equal(last, good, "the worked scan")
+    assert stats[:, :, 0].sum() > 0
+    for key, i, v, fragment in broken:
+        t = {k: a.copy() for k, a in good.items()}
+        t[key][i] = v
+        with pytest.raises(McError, match=fragment) as e:
+            ctx.ev_add_matches(t)
+        assert e.value.code == 1, f"{key}[{i}] = {v}: {e.value}"
+        ap2, stats2 = ctx.ev_ap()
+        assert ap2.tobytes() == ap.tobytes() and stats2.tobytes() == stats.tobytes(), f"{key}[{i}] = {v}"
+        R.assert_tables_equal(ctx.ev_scan(), last, f"last scan after {key}[{i}] = {v}")
+    ctx.ev_add_matches(good)                              # and the valid table still adds
+    twice = new_ctx()
+    twice.ev_begin(CLS, None, 100, False)
+    twice.ev_add_matches(good)
+    twice.ev_add_matches(good)
+    for x, y in zip(ctx.ev_ap(), twice.ev_ap()):
+        assert x.tobytes() == y.tobytes()
+    assert (ctx.ev_ap()[1][:, :, 0] == 2 * stats[:, :, 0]).all()
