@@ -82,31 +82,29 @@ std::vector<int32_t> pp_dbscan(mc_ctx *ctx, PPRun &r)
         if (const char *e = getenv("MC_PP_BIG_MIN")) big_min = std::max(1, atoi(e));
         std::vector<mc::PPInt2> items;
         const int nbig = mc::pp_big_items(r.h_npoff.data(), r.h_order.data(), N, big_min, items);
+        mc::PPNodes b{a.npoff, r.xyz.as<double>(), r.pcell.as<unsigned long long>(), r.pbkt.as<int>(), r.bcnt.as<int>(),
+                      r.bstart.as<int>(), r.blist.as<int>(), r.ncnt.as<int>(), r.par.as<int>(), r.root.as<int>(),
+                      r.rnk.as<int>(), r.lab.as<int>(), r.ccnt.as<int>(), r.nob.as<int>(), r.nsh.as<int>(), nullptr,
+                      r.skey.as<unsigned long long>(), r.sxyz.as<double>(), r.sidx.as<int>()};
         if (nbig) {
             DevBuf ditems, gcm;
             pp_upload(s, ditems, items.data(), items.size() * sizeof(int2));
             gcm.reserve(static_cast<size_t>(N) * 12 + 8);
-            const mc::PPBig b{a.npoff, r.xyz.as<double>(), r.pcell.as<unsigned long long>(), r.pbkt.as<int>(),
-                              r.bcnt.as<int>(), r.bstart.as<int>(), r.blist.as<int>(), r.ncnt.as<int>(), r.par.as<int>(),
-                              r.root.as<int>(), r.rnk.as<int>(), r.lab.as<int>(), r.ccnt.as<int>(), gcm.as<int>()};
+            b.gcm = gcm.as<int>();
             const int ni = static_cast<int>(items.size());
             hipLaunchKernelGGL(mc::k_pp_big_grid<512>, dim3(nbig), dim3(512), 0, s, nbig, r.dorder.as<int>(), r.pr, b);
             hipLaunchKernelGGL((mc::k_pp_big_walk<512, 0>), dim3(std::min(ni, 65536)), dim3(512), 0, s, ni,
                                ditems.as<int2>(), r.pr, b);
             hipLaunchKernelGGL((mc::k_pp_big_walk<512, 1>), dim3(std::min(ni, 65536)), dim3(512), 0, s, ni,
                                ditems.as<int2>(), r.pr, b);
-            hipLaunchKernelGGL(mc::k_pp_big_label<512>, dim3(nbig), dim3(512), 0, s, nbig, r.dorder.as<int>(), r.pr, b,
-                               r.nob.as<int>(), r.nsh.as<int>());
+            hipLaunchKernelGGL(mc::k_pp_big_label<512>, dim3(nbig), dim3(512), 0, s, nbig, r.dorder.as<int>(), r.pr, b);
             MC_HIP(hipGetLastError());
             MC_HIP(hipStreamSynchronize(s));  // ditems / gcm are freed at scope exit
+            b.gcm = nullptr;                  // (k_pp_dbscan keeps cmax in registers)
         }
         if (N > nbig)  // 512-thread workgroups (1024 spills the neighbour walks)
             hipLaunchKernelGGL(mc::k_pp_dbscan<512>, dim3(std::max(1, std::min(N - nbig, ctx->num_cu * 2))), dim3(512), 0, s,
-                               N - nbig, r.dorder.as<int>() + nbig, r.tick.as<int>(), a.npoff, r.pr, r.xyz.as<double>(),
-                               r.pcell.as<unsigned long long>(), r.pbkt.as<int>(), r.bcnt.as<int>(), r.bstart.as<int>(),
-                               r.blist.as<int>(), r.ncnt.as<int>(), r.par.as<int>(), r.root.as<int>(), r.rnk.as<int>(),
-                               r.lab.as<int>(), r.ccnt.as<int>(), r.nob.as<int>(), r.nsh.as<int>(),
-                               r.skey.as<unsigned long long>(), r.sxyz.as<double>(), r.sidx.as<int>());
+                               N - nbig, r.dorder.as<int>() + nbig, r.tick.as<int>(), r.pr, b);
         MC_HIP(hipGetLastError());
     }
     std::vector<int32_t> h_nob(N), base(N + 1, 0);

@@ -1,4 +1,4 @@
-"""Inputs that take post-processing (mc_pp_run, mc_pp_run_device: csrc/mc_pp_kernels.inl, mc_pp_host.inl) past
+"""Inputs that take post-processing (mc_pp_run, mc_pp_run_device: csrc/mc_pp_*.inl) past
 one frame word, past its object windows, to its node-size threshold, past its slot count and onto its rules.
 Pure numpy.  test_pp_limit_inputs_cpu.py asserts without a GPU that every case reaches what it is for;
 test_gpu_pp_limits.py compares the device with oracle/pp_oracle.py on them, bit for bit.
@@ -379,6 +379,17 @@ def _edge_noise(with_noise):
     return _all_seen(s)
 
 
+def _edge_no_core():
+    """a node of three points within eps of each other: nobody has min_points neighbours, so there is no core point
+    and no cluster, and the noise class is the node's only object; beside it a node of one cluster and no noise"""
+    s = _Scene(2)
+    a = s.points(np.array([[0, 0, 0], [0, 31 * U, 0], [0, 0, 31 * U]]))
+    b = s.points(_square(5.0, 0.0))
+    s.node([s.mask(a, 0), s.mask(a, 1)], None, a)
+    s.node([s.mask(b, 0), s.mask(b, 1)], None, b)
+    return _all_seen(s)
+
+
 RATIO_EQ = 1 / (2 + 1e-6)                                             # a point hit in 1 of the 2 frames it is seen in
 
 
@@ -440,7 +451,7 @@ def _edge_repre():
 EDGE_CASES = {
     "eps_at": lambda: _edge_eps(False), "eps_below": lambda: _edge_eps(True),
     "border_y_first": lambda: _edge_border(False), "border_x_first": lambda: _edge_border(True),
-    "noise_last": lambda: _edge_noise(True), "noise_none": lambda: _edge_noise(False),
+    "noise_last": lambda: _edge_noise(True), "noise_none": lambda: _edge_noise(False), "no_core": _edge_no_core,
     "ratio_at": lambda: _edge_ratio(RATIO_EQ), "ratio_below": lambda: _edge_ratio(np.nextafter(RATIO_EQ, 0)),
     "ratio_negative": lambda: _edge_ratio(-1.0),
     "merge_4_of_5": lambda: _edge_merge(5, 10, 4), "merge_5_of_6": lambda: _edge_merge(6, 10, 5),

@@ -10,13 +10,15 @@ prediction matrix, host and device copies).
 Each case catches a one-token change of the kernels made for it; each was built into a library of its own and
 this file run against it once on an MI355X, where exactly the tests named failed (as comparisons, not faults):
 
-  change (mc_pp_kernels.inl)                                               tests that fail
+  change (k_pp_filter, pp_wave_argmax: mc_pp_filter.inl; k_pp_prep,
+  k_pp_cl_gather: mc_pp_layout.inl; k_pp_dbscan and its steps:
+  mc_pp_dbscan.inl; k_pp_decide: mc_pp_merge.inl)                          tests that fail
   k_pp_filter: hit word  fp >> 6  ->  0                                    f65, f128, f129, f200, shifted, drop-in f129
   k_pp_prep: rank loop  w < (col >> 6)  ->  w < 0                          the same and the clustered entry
   k_pp_filter: cvid loop  w < FW  ->  w < 1                                the same
   k_pp_filter: cnode loop  w < W  ->  w < 1                                the same
   k_pp_cl_gather: w < FW  ->  w < 1                                        the clustered entry alone
-  k_pp_dbscan: cell of  P - mn[c]  ->  P - 0.0                             shifted (and the other cases off the origin)
+  k_pp_dbscan (pp_grid): cell of  P - mn[c]  ->  P - 0.0                   shifted (and the other cases off the origin)
   k_pp_filter step 3: obj_box[ob + c0 + c]  ->  [ob + 0 + c]               obj257, obj1025, obj2049 alone
   k_pp_filter step 2: c0 += kPPObjChunk  ->  c0 += no  (one window)        obj1025, obj2049 alone
   pp_wave_argmax: oi < ix  ->  oi > ix                                     obj1025, obj2049 (and every other tie)
@@ -132,6 +134,17 @@ def test_rule_edges(name):
     if name == "repre":
         r = _ctx().pp_export()
         assert r["obj_repre"][0].tolist() == pl.REPRE_TOP and r["obj_repre"][1].tolist() == [2, 0, 1, -1, -1]
+
+
+@pytest.mark.parametrize("name", ["border_y_first", "border_x_first", "noise_last", "noise_none", "no_core"])
+def test_rule_edges_on_split_route(name, monkeypatch):
+    """MC_PP_BIG_MIN = 1 sends these nodes of 3 to 9 points through k_pp_big_grid, k_pp_big_walk and k_pp_big_label:
+    the border rule, the noise class with and without members, and a node without a core point through the shared
+    steps' second caller and the bucket-list walk (the n8193 nodes hold no border point and only one noise point)"""
+    monkeypatch.setenv("MC_PP_BIG_MIN", "1")
+    sizes = [len(n[2]) for n in pl.built("edges/" + name).onodes]
+    assert pl.big_items(sizes, 1)[0] == len(sizes)
+    _both_entries("edges/" + name)
 
 
 def test_extent_limit():

@@ -121,6 +121,7 @@ def test_wide_cases():
     ok, refused = pl.built("wide"), pl.WIDE_REFUSED()
     assert np.floor(np.ptp(ok.scene[:, 0]) / ce) == 2 ** 21 - 2 and np.floor(np.ptp(refused.scene[:, 0]) / ce) == 2 ** 21 - 1
     assert "static_cast<double>((1 << 21) - 1)" in pl._src("mc_pp_kernels.inl")
+    assert "< kPPMaxCells))" in pl._src("mc_pp_layout.inl")        # k_pp_prep's test against it
     wp, wm, det = pl.oracle("wide")
     assert [len(p) for p in wp] == [4, 4]
 
@@ -146,6 +147,9 @@ def test_edge_variants_decide_as_stated():
     assert c.onodes[0][2][0] == q
     assert pts("border_y_first") == [sorted(y + [q]), x] and pts("border_x_first") == [sorted(x + [q]), y]
     assert pts("noise_last") == [[4], [0, 1, 2, 3]] and pts("noise_none") == [[0, 1, 2, 3]]
+    assert pts("no_core") == [[0, 1, 2], [3, 4, 5, 6]]
+    labs = [r["lab"].tolist() for r in pl.oracle("edges/no_core")[2]["nodes"]]
+    assert labs == [[0, 0, 0], [1, 1, 1, 1]]                      # all noise (class 0); one cluster and no noise
     m = pl.built("edges/ratio_at").meta
     every = set(range(6))
     assert set(pts("ratio_at")[0]) == every - {m["t"], m["z"]} and m["u"] in pts("ratio_at")[0]
