@@ -3,10 +3,46 @@
 // global-memory kernel for slots beyond the largest class.
 namespace mc {
 
+// a slot's grid in global memory, as mc_bp_ring.hpp's ring_mark and ring_walk read it (kept records only)
+struct BpRingGrid {
+    const double4 *pt;
+    const int *bs;
+    unsigned nb;
+    // (no bounds test: coordinates are >= -2 (the origin lies below every point) and far below
+    // kBpCellMax; a negative one makes a key with its top bits set, which no record has)
+    __device__ __forceinline__ unsigned bucket(int x, int y, int z) const { return mod_mul(bp_hash3(x, y, z), nb); }
+    __device__ __forceinline__ int start(unsigned b) const { return bs[b]; }
+    __device__ __forceinline__ double4 rec(int q) const { return pt[q]; }
+    __device__ __forceinline__ unsigned long long key(const double4 &p) const
+    {
+        return static_cast<unsigned long long>(__double_as_longlong(p.w));
+    }
+    __device__ __forceinline__ unsigned long long cell_key(int x, int y, int z) const { return pack3(x, y, z) | kKeptBit; }
+};
+// a thread's cell and offsets (RingWhere's members), parked in LDS: component k at [k * 256 + thread].  The
+// walk uses them once per cell it takes, not per record, and the kernel has no registers to spare beside the
+// k-NN list (128 at four waves per SIMD); volatile, or the reads would be hoisted into registers again
+struct BpRingWhere {
+    const volatile __attribute__((address_space(3))) int *c;
+    const volatile __attribute__((address_space(3))) double *o;
+    __device__ __forceinline__ int x() const { return c[0]; }
+    __device__ __forceinline__ int y() const { return c[256]; }
+    __device__ __forceinline__ int z() const { return c[512]; }
+    __device__ __forceinline__ double ox() const { return o[0]; }
+    __device__ __forceinline__ double oy() const { return o[256]; }
+    __device__ __forceinline__ double oz() const { return o[512]; }
+};
+
 // (a4) k-NN of the deferred points of every LDS-class slot of a batch (k_bp_denoise_lds's list pass
-// could not serve them): a thread per queued point, over its slot's grid in global memory.  Grid rings up to R = 2 (cells whose nearest face is no nearer than the current k-th
-// distance skipped: a's offsets in its cell, gaps shrunk by 1e-9 ce so the bound stays below every
-// point's computed distance); a point the rings cannot settle (sparse) scans every kept point.
+// could not serve them): a thread per queued point, over its slot's grid in global memory.  The 27
+// cells around the point's, then the shell of 98 around those (R = 1, R = 2), each ring marked and
+// walked by the lane on its own (mc_bp_ring.hpp): cells whose nearest face is no nearer than the
+// lane's current k-th distance are skipped (a's offsets in its cell, gaps shrunk by 1e-9 ce so the
+// bound stays below every point's computed distance), the bucket bounds of the others are read in
+// groups, and only the cells whose bucket holds records are walked, in one loop per ring: a wave
+// takes as many trips as its longest lane has record pairs, not a dependent bounds read per cell of
+// the cube (most cells of a surface patch are empty).  A point the rings cannot settle (sparse)
+// scans every kept point.
 template <int WPE = 1>
 __global__ __launch_bounds__(256, WPE) void k_bp_knn_ring(const int *__restrict__ dq_cnt, const int *__restrict__ dq,
                                                      const int *__restrict__ slot_pix, const int *__restrict__ slot_m,
@@ -15,6 +51,8 @@ __global__ __launch_bounds__(256, WPE) void k_bp_knn_ring(const int *__restrict_
                                                      const double *__restrict__ slot_grid, double *__restrict__ gavg,
                                                      int *__restrict__ err)
 {
+    __shared__ int s_c[3 * 256];
+    __shared__ double s_o[3 * 256];
     const int ne = *dq_cnt;
     const int lane = lane_id();
     // wave-uniform loop (a wave's 64 points together), so that the whole wave can take a sparse
@@ -63,30 +101,31 @@ __global__ __launch_bounds__(256, WPE) void k_bp_knn_ring(const int *__restrict_
         if (active) {
             a = g.pt[q];
             unpack3(static_cast<unsigned long long>(__double_as_longlong(a.w)) & ~kKeptBit, x, y, z);
-            auto take = [&](int, double d2) {
-                sorted_insert(best, d2);
-                found++;
-            };
             ox = fmin(fmax(a.x - mn[0] - x * ce, 0.0), ce);
             oy = fmin(fmax(a.y - mn[1] - y * ce, 0.0), ce);
             oz = fmin(fmax(a.z - mn[2] - z * ce, 0.0), ce);
-            auto gap = [&](int d, double o) {
-                return d == 0 ? 0.0 : fmax(0.0, (d > 0 ? d * ce - o : -d * ce - (ce - o)) - sl);
-            };
-            for (int R = 0; R <= 2 && !done; R++) {
-                for (int dz = -R; dz <= R; dz++)
-                    for (int dy = -R; dy <= R; dy++) {
-                        const bool edge = dz == -R || dz == R || dy == -R || dy == R;
-                        const int step = (edge || R == 0) ? 1 : 2 * R;
-                        const double gyz = gap(dy, oy) * gap(dy, oy) + gap(dz, oz) * gap(dz, oz);
-                        for (int dx = -R; dx <= R; dx += step) {
-                            if (gyz + gap(dx, ox) * gap(dx, ox) >= best[kBpKnnMax - 1]) continue;
-                            lds_cell(g, x + dx, y + dy, z + dz, kKeptBit, a.x, a.y, a.z, take);
-                        }
-                    }
-                const double reach = static_cast<double>(R) * ce;
-                done = found >= kBpKnnMax && best[kBpKnnMax - 1] < reach * reach * (1.0 - 1e-9);
-            }
+        }
+        s_c[threadIdx.x] = x;
+        s_c[256 + threadIdx.x] = y;
+        s_c[512 + threadIdx.x] = z;
+        s_o[threadIdx.x] = ox;
+        s_o[256 + threadIdx.x] = oy;
+        s_o[512 + threadIdx.x] = oz;
+        const BpRingWhere wh{(const volatile __attribute__((address_space(3))) int *)(s_c + threadIdx.x),
+                             (const volatile __attribute__((address_space(3))) double *)(s_o + threadIdx.x)};
+        const BpRingGrid rg{g.pt, g.bs, g.nb};
+#pragma unroll 1
+        for (int ring = 0; ring < 2; ring++) {  // rolled: one copy of the walk (instruction cache)
+            if (!active || done) continue;
+            const RingMask m = ring_mark(rg, ring, wh, ce, sl, best[kBpKnnMax - 1]);
+            ring_walk(
+                rg, ring, m, wh, a.x, a.y, a.z, ce, sl, [&] { return best[kBpKnnMax - 1]; },
+                [&](double d2, bool on) {
+                    sorted_insert(best, on ? d2 : DBL_MAX);
+                    found += on ? 1 : 0;
+                });
+            const double reach = static_cast<double>(ring + 1) * ce;
+            done = found >= kBpKnnMax && best[kBpKnnMax - 1] < reach * reach * (1.0 - 1e-9);
         }
 #ifdef MC_BP_RING_NOFB
         done = true;  // timing-only diagnostics build: no whole-cloud fallback (wrong results)

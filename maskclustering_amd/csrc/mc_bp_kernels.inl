@@ -48,6 +48,7 @@
 #include "mc_internal.hpp"
 #include "mc_bp_knnsel.hpp"
 #include "mc_bp_qcell.hpp"
+#include "mc_bp_ring.hpp"
 #include "mc_bp_world.hpp"
 
 #include <cfloat>
