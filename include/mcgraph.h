@@ -174,6 +174,17 @@ int mc_backproject_get_batching(mc_ctx *ctx, int64_t *out4);
 int mc_backproject_get_masks(mc_ctx *ctx, int32_t *mask_col, int32_t *mask_label, int64_t *mask_off,
                              int32_t *mask_pts);
 int mc_backproject_get_candidates(mc_ctx *ctx, int32_t *stats /* num_candidates * MC_BP_NSTAT */);
+/* test read-back of S1's pixel lists and voxel means (no reference counterpart), of a call whose frames
+ * ran as exactly one batch (the arrays are per batch; otherwise, or after no call, MC_ERR_STATE).  Call
+ * once with sizes3 alone, then with the arrays (any of them may be NULL):
+ *   sizes3  = {slots (= num_candidates, in that order), their pixels in all, their voxels in all}
+ *   slots   [slots * 4]    frame, id, pixel count, voxel count
+ *   pixels  [pixels]       slot after slot, each slot's valid pixels v * width + u in list order
+ *   means   [voxels * 3]   slot after slot, each slot's voxel means in voxel order
+ *   origins [slots * 3]    each slot's voxel grid origin (min bound - voxel_size / 2)
+ *   handed2 = {slots the first voxel tier handed to the second, slots the second handed to the global hash} */
+int mc_backproject_get_voxels(mc_ctx *ctx, int64_t *sizes3, int32_t *slots, uint32_t *pixels, double *means,
+                              double *origins, int32_t *handed2);
 /* mask_pts into a device buffer (stream-ordered on the context stream, no host copy): the
  * frame-sharded path all-gathers the per-rank point lists over RCCL;
  * mask_col / mask_label / mask_off come from mc_backproject_get_masks with mask_pts = NULL */

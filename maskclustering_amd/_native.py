@@ -34,7 +34,8 @@ EXPORTED = [
     "mc_cluster_get_edge_counts", "mc_cluster_get_final_labels", "mc_cluster_get_objects",
     "mc_bp_params_default", "mc_scene_set_points", "mc_backproject", "mc_backproject_frames", "mc_backproject_frames_raw",
     "mc_backproject_get_info", "mc_backproject_get_batching",
-    "mc_backproject_get_masks", "mc_backproject_get_candidates", "mc_scene_use_backprojection",
+    "mc_backproject_get_masks", "mc_backproject_get_candidates", "mc_backproject_get_voxels",
+    "mc_scene_use_backprojection",
     "mc_backproject_copy_points_device",
     "mc_pp_run", "mc_pp_get_info", "mc_pp_get_results", "mc_pp_run_device", "mc_pp_run_clustered",
     "mc_pp_export_info", "mc_pp_export", "mc_pp_export_pred_masks", "mc_eval_match_counts", "mc_frames_decode",
@@ -183,6 +184,7 @@ def load():
         "mc_backproject_get_masks": (ctypes.c_int, [vp, vp, vp, vp, vp]),
         "mc_backproject_copy_points_device": (ctypes.c_int, [vp, vp]),
         "mc_backproject_get_candidates": (ctypes.c_int, [vp, vp]),
+        "mc_backproject_get_voxels": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "mc_scene_use_backprojection": (ctypes.c_int, [vp]),
         "mc_pp_run": (ctypes.c_int, [vp, P(PPParams), i64, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "mc_pp_get_info": (ctypes.c_int, [vp, P(PPInfo)]),
@@ -716,11 +718,32 @@ def _bp_methods():
         self._check(self.L.mc_backproject_get_candidates(self.h, _ptr(st)))
         return st[:n]
 
+    def bp_voxels(self) -> dict:
+        """mc_backproject_get_voxels: the pixel lists and voxel means of the last call's slots (a call of one
+        batch), in candidate order: slots [NS,4] (frame, id, pixels, voxels), pixels / means / origin as
+        per-slot lists, handed = (slots the first voxel tier handed on, slots the second did)."""
+        sizes = np.zeros(3, np.int64)
+        self._check(self.L.mc_backproject_get_voxels(self.h, _ptr(sizes), None, None, None, None, None))
+        ns, npx, nvx = (int(x) for x in sizes)
+        slots = np.zeros((max(ns, 1), 4), np.int32)
+        pix = np.zeros(max(npx, 1), np.uint32)
+        means = np.zeros((max(nvx, 1), 3), np.float64)
+        origin = np.zeros((max(ns, 1), 3), np.float64)
+        handed = np.zeros(2, np.int32)
+        self._check(self.L.mc_backproject_get_voxels(self.h, _ptr(sizes), _ptr(slots), _ptr(pix), _ptr(means),
+                                                     _ptr(origin), _ptr(handed)))
+        slots = slots[:ns]
+        po = np.concatenate([[0], np.cumsum(slots[:, 2], dtype=np.int64)])
+        vo = np.concatenate([[0], np.cumsum(slots[:, 3], dtype=np.int64)])
+        return dict(slots=slots, pixels=[pix[po[i]:po[i + 1]] for i in range(ns)],
+                    means=[means[vo[i]:vo[i + 1]] for i in range(ns)], origin=origin[:ns],
+                    handed=(int(handed[0]), int(handed[1])))
+
     def use_backprojection(self):
         self._check(self.L.mc_scene_use_backprojection(self.h))
 
     for f in (set_points, backproject, backproject_frames, bp_info, bp_batching, bp_masks, bp_mask_index,
-              bp_points_to_device, bp_candidates, use_backprojection):
+              bp_points_to_device, bp_candidates, bp_voxels, use_backprojection):
         setattr(Context, f.__name__, f)
 
 

@@ -713,6 +713,7 @@ void bp_run(mc_ctx *ctx, int F, int H, int W, BpFrames src, const mc_bp_params *
     bp.col.clear(), bp.label.clear(), bp.stats.clear();
     bp.off.assign(1, 0);
     bp.nnz = 0;
+    bp.batches = 0;
     const float rf = static_cast<float>(prm.ball_radius);
     if (bp.grid_radius != rf) {  // a new scene (mc_scene_set_points) or radius: the 2r scene grid
         TimedScope ts(ctx->timer, s, "bp_grid");
@@ -771,6 +772,9 @@ void bp_run(mc_ctx *ctx, int F, int H, int W, BpFrames src, const mc_bp_params *
             bp.tmp.reserve(tmp_cap * 4);
             continue;
         }
+        bp.batches++;
+        bp.vx_handed[0] = hs[BS_VXFB];
+        bp.vx_handed[1] = hs[BS_VXFB2];
         pend = bp_emit_pack(ctx, s, bt, hs);
         b0 += fb;
     }
@@ -924,6 +928,72 @@ int mc_backproject_get_candidates(mc_ctx *ctx, int32_t *stats)
     return guarded(ctx, [&] {
         MC_REQUIRE(ctx->bp.have_result, MC_ERR_STATE, "no back-projection result");
         std::copy(ctx->bp.stats.begin(), ctx->bp.stats.end(), stats);
+    });
+}
+
+int mc_backproject_get_voxels(mc_ctx *ctx, int64_t *sizes3, int32_t *slots, uint32_t *pixels, double *means,
+                              double *origins, int32_t *handed2)
+{
+    return guarded(ctx, [&] {
+        const BpState &bp = ctx->bp;
+        MC_REQUIRE(bp.have_result, MC_ERR_STATE, "no back-projection result");
+        MC_REQUIRE(bp.batches == 1, MC_ERR_STATE,
+                   "the voxel stage's arrays hold one batch: the last call ran " + std::to_string(bp.batches) +
+                       " batches (mc_backproject_get_voxels needs exactly one)");
+        MC_REQUIRE(sizes3, MC_ERR_INVALID, "null sizes");
+        hipStream_t s = ctx->stream;
+        // the slots of the batch are the call's candidates, in their order (frame, then id)
+        const size_t NS = bp.stats.size() / MC_BP_NSTAT;
+        std::vector<int32_t> sp(NS + 1, 0), snv(NS + 1, 0);
+        if (NS) {
+            MC_HIP(hipMemcpyAsync(sp.data(), bp.slot_pix.ptr, NS * 4, hipMemcpyDeviceToHost, s));
+            MC_HIP(hipMemcpyAsync(snv.data(), bp.slot_nv.ptr, NS * 4, hipMemcpyDeviceToHost, s));
+            MC_HIP(hipStreamSynchronize(s));
+        }
+        size_t npx = 0, nvx = 0, span = 0;  // span: pixel-list positions the slots' ranges reach
+        for (size_t x = 0; x < NS; x++) {
+            const int32_t *row = bp.stats.data() + x * MC_BP_NSTAT;
+            MC_REQUIRE(sp[x] >= 0 && row[2] >= 0 && static_cast<size_t>(sp[x]) + row[2] <= bp.px_cap && snv[x] == row[3] &&
+                           snv[x] <= row[2],
+                       MC_ERR_HIP, "slot arrays differ from the call's candidates (internal error)");
+            npx += row[2];
+            nvx += snv[x];
+            span = std::max(span, static_cast<size_t>(sp[x]) + row[2]);
+        }
+        sizes3[0] = static_cast<int64_t>(NS);
+        sizes3[1] = static_cast<int64_t>(npx);
+        sizes3[2] = static_cast<int64_t>(nvx);
+        if (handed2) {
+            handed2[0] = bp.vx_handed[0];
+            handed2[1] = bp.vx_handed[1];
+        }
+        for (size_t x = 0; slots && x < NS; x++) {
+            const int32_t *row = bp.stats.data() + x * MC_BP_NSTAT;
+            const int32_t out[4] = {row[0], row[1], row[2], row[3]};
+            std::copy(out, out + 4, slots + 4 * x);
+        }
+        if (!NS) return;
+        if (pixels) {
+            std::vector<uint32_t> pl(span + 1);
+            MC_HIP(hipMemcpyAsync(pl.data(), bp.pix_list.ptr, span * 4, hipMemcpyDeviceToHost, s));
+            MC_HIP(hipStreamSynchronize(s));
+            for (size_t x = 0, o = 0; x < NS; o += bp.stats[x * MC_BP_NSTAT + 2], x++)
+                std::copy(pl.begin() + sp[x], pl.begin() + sp[x] + bp.stats[x * MC_BP_NSTAT + 2], pixels + o);
+        }
+        if (means) {
+            std::vector<double> vp(3 * span + 1);
+            MC_HIP(hipMemcpyAsync(vp.data(), bp.vpts.ptr, 3 * span * 8, hipMemcpyDeviceToHost, s));
+            MC_HIP(hipStreamSynchronize(s));
+            for (size_t x = 0, o = 0; x < NS; o += snv[x], x++)
+                std::copy(vp.begin() + 3 * static_cast<size_t>(sp[x]), vp.begin() + 3 * (static_cast<size_t>(sp[x]) + snv[x]),
+                          means + 3 * o);
+        }
+        if (origins) {
+            std::vector<double> sg(8 * NS);
+            MC_HIP(hipMemcpyAsync(sg.data(), bp.slot_grid.ptr, 8 * NS * 8, hipMemcpyDeviceToHost, s));
+            MC_HIP(hipStreamSynchronize(s));
+            for (size_t x = 0; x < NS; x++) std::copy(sg.begin() + 8 * x, sg.begin() + 8 * x + 3, origins + 3 * x);
+        }
     });
 }
 

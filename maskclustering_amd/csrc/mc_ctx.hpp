@@ -74,6 +74,10 @@ struct BpState {
     DevBuf pts;  // the masks' point lists
     std::vector<int32_t> col, label, stats;
     std::vector<int64_t> off;
+    // the voxel stage's read-back (mc_backproject_get_voxels): the batches the last call accepted (the per-batch
+    // arrays hold the last one's slots), and the slots the accepted batch's voxel tiers handed on
+    int batches = 0;
+    int vx_handed[2] = {0, 0};
 };
 
 // AP evaluation state of a context (the host code is mc_ap_host.inl; EvTables is mc_ap_plan.hpp's)
