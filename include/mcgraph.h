@@ -598,6 +598,52 @@ int mc_proj_top_views(mc_ctx *ctx, const double *points, int32_t num_frames, con
                       int32_t *top_pos, int32_t *top_frame, int32_t *boxes, int32_t *status, int32_t *inside,
                       int out_on_device);
 
+/* ---- scene point cloud from RGB-D frames ------------------------------------------------------------
+ * Replaces backproject + create_downsampled_point_cloud (tasmap/tasmap2mct_format.py:216-284), the
+ * producer of a TASMap scene's points.  DESIGN.md §2 (f7).
+ *
+ * mc_cloud_fuse_frames: frames in order; depth float32 [F, H, W] (metres), rgb uint8 [F, H, W, 3],
+ * intrinsics float64 [F, 4] = fx, fy, cx, cy, poses float64 [F, 16] row-major camera -> world;
+ * on_device applies to all four.  A pixel (v, u) is kept iff 0 < d < depth_trunc (NaN, +-inf, 0,
+ * negative and d == depth_trunc are dropped), pixels row-major; its point is S1's (z = (double)d,
+ * x = ((u - cx) z) / fx, y = ((v - cy) z) / fy, the pose as ((T0 x + T1 y) + T2 z) + T3 per row without
+ * FMA, then the divide by row 3); its colour (r, g, b) / 255.0 in float64.  buffer_frames consecutive
+ * frames make a buffer, flushed when (i + 1) % buffer_frames == 0 and, if non-empty, after the
+ * last frame; a flush is voxel_down_sample(voxel_size) of the buffer's points, frame-major then
+ * pixel order; the flushed results are concatenated in order and voxel_down_sample'd once more.
+ * voxel_down_sample: vmin = min - voxel / 2 per axis, index = floor((p - vmin) / voxel) (a rounded
+ * subtraction, a rounded division), a voxel's sums of points and colours are the LEFT FOLD IN INPUT
+ * ORDER in float64, mean = sum / count, output order = order of each voxel's first input point.
+ * (Open3D's own order and summation order are its hash map's: parity-unpinned, as for S1.)
+ * The result stays on the device with the context.  An empty result (no valid pixel, F == 0) is valid.
+ *
+ * mc_cloud_voxel_down: one voxel_down_sample of points float64 [n, 3] with colours float64 [n, 3] or
+ * NULL (then the result has no colours), by the same device routine.
+ *
+ * mc_cloud_info: out[5] = result points, voxel_down_sample runs of the call (empty ones included),
+ * the largest run's input points, the largest voxel population seen, bytes the result holds.
+ * mc_cloud_get: the result's points and colours (float64 [n, 3] each; either may be NULL) to host
+ * arrays or, with on_device, device pointers.
+ * mc_scene_use_cloud: the result's points rounded to float32 (to nearest) become the scene points,
+ * on the device; equal in effect to mc_scene_set_points of that array.
+ *
+ * Every check precedes the first write of context state: a refused call leaves the earlier result.
+ * MC_ERR_INVALID: a non-finite pose or intrinsic entry, voxel_size <= 0, buffer_frames < 1, a
+ * non-finite point.  MC_ERR_UNSUPPORTED: a voxel_down_sample run spanning 2^21 voxels or more on an
+ * axis, one of 2^31 points or more, one whose arrays exceed mc_ctx_set_memory_budget (the message
+ * names the bytes; without a budget four fifths of the free device memory).  MC_ERR_STATE:
+ * mc_cloud_info, mc_cloud_get or mc_scene_use_cloud before a result, colours of a result without. */
+typedef struct { double voxel_size, depth_trunc; int32_t buffer_frames; } mc_cloud_params;
+void mc_cloud_params_default(mc_cloud_params *p);
+int mc_cloud_fuse_frames(mc_ctx *ctx, int32_t num_frames, int32_t height, int32_t width, const float *depth,
+                         const uint8_t *rgb, const double *intrinsics, const double *poses, int on_device,
+                         const mc_cloud_params *params);
+int mc_cloud_voxel_down(mc_ctx *ctx, int64_t num_points, const double *points, const double *colors, double voxel_size,
+                        int on_device);
+int mc_cloud_info(mc_ctx *ctx, int64_t *out5);
+int mc_cloud_get(mc_ctx *ctx, double *points, double *colors, int on_device);
+int mc_scene_use_cloud(mc_ctx *ctx);
+
 /* host utility: packed little-endian bit rows (bit c of word c/64 = column c) -> one byte per
  * column, rows * ncols bytes (the dense bool point_frame_matrix the reference's callers read,
  * graph/construction.py:40,52), split over host threads.                                      */

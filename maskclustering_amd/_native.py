@@ -47,6 +47,8 @@ EXPORTED = [
     "mc_ev_ap", "mc_ev_get_curve", "mc_ev_state_info", "mc_ev_state_export", "mc_ev_state_merge",
     "mc_crop_params_default", "mc_crop_boxes", "mc_crop_render", "mc_crop_coeffs",
     "mc_proj_boxes", "mc_proj_top_views",
+    "mc_cloud_params_default", "mc_cloud_fuse_frames", "mc_cloud_voxel_down", "mc_cloud_info", "mc_cloud_get",
+    "mc_scene_use_cloud",
 ]
 MC_COMM_ID_BYTES = 128
 
@@ -117,6 +119,13 @@ class CropParams(ctypes.Structure):
 
 
 MC_CROP_OK, MC_CROP_ABSENT, MC_CROP_EMPTY = 0, 1, 2
+
+
+class CloudParams(ctypes.Structure):
+    """mc_cloud_params: the voxel size (what tasmap2mct_format.py:240 calls depth_trunc=0.005), the depth
+    limit (its DEPTH_LIMIT = 20) and the frames of a buffer (buffer_size)."""
+    _fields_ = [("voxel_size", ctypes.c_double), ("depth_trunc", ctypes.c_double), ("buffer_frames", ctypes.c_int32)]
+
 
 _lib = None
 
@@ -232,6 +241,12 @@ def load():
                                          vp, ctypes.c_int]),
         "mc_proj_top_views": (ctypes.c_int, [vp, vp, i32, vp, vp, i32, i32, ctypes.c_int, i32, vp, vp, vp, vp, vp,
                                              ctypes.c_int]),
+        "mc_cloud_params_default": (None, [P(CloudParams)]),
+        "mc_cloud_fuse_frames": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, ctypes.c_int, P(CloudParams)]),
+        "mc_cloud_voxel_down": (ctypes.c_int, [vp, i64, vp, vp, dbl, ctypes.c_int]),
+        "mc_cloud_info": (ctypes.c_int, [vp, vp]),
+        "mc_cloud_get": (ctypes.c_int, [vp, vp, vp, ctypes.c_int]),
+        "mc_scene_use_cloud": (ctypes.c_int, [vp]),
     }
     # MCGRAPH_LIB_PARTIAL=1 (A/B scripts only): an older variant library may lack newer entry points
     partial = os.environ.get("MCGRAPH_LIB_PARTIAL") == "1"
@@ -1294,6 +1309,109 @@ def _proj_methods():
 
 
 _proj_methods()
+
+
+CLOUD_INFO = ["num_points", "stages", "max_stage_points", "max_voxel_population", "bytes_held"]
+
+
+def _cloud_methods():
+    def _on_device(*arrays):
+        dev = [hasattr(a, "data_ptr") and a.device.type == "cuda" for a in arrays if a is not None]
+        if any(dev) and not all(dev):
+            raise ValueError("all arrays on the host, or all tensors on the context's device")
+        return bool(dev) and all(dev)
+
+    def _settle(self):
+        """work queued on torch's current stream is waited for when the context runs on another one"""
+        import torch
+        cur = torch.cuda.current_stream(self.torch_device)
+        if (cur.cuda_stream or 0) != (self.stream() or 0):
+            cur.synchronize()
+
+    def _arg(a, dt, shape, name, device):
+        if device:
+            import torch
+            if a.dtype != getattr(torch, dt) or not a.is_contiguous() or tuple(a.shape) != tuple(shape):
+                raise ValueError(f"{name}: a contiguous {dt} device tensor of shape {tuple(shape)}")
+            return a, (ctypes.c_void_p(a.data_ptr()) if a.numel() else None)
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{name}: shape {tuple(shape)} expected, got {tuple(a.shape)}")
+        a = np.ascontiguousarray(a, dt)
+        return a, (_ptr(a) if a.size else None)
+
+    def cloud_fuse(self, depth, rgb, intrinsics, poses, params: CloudParams | None = None):
+        """mc_cloud_fuse_frames: depth float32 [F, H, W], rgb uint8 [F, H, W, 3], intrinsics float64 [F, 4]
+        = fx, fy, cx, cy, poses float64 [F, 4, 4]; all numpy, or all tensors on the context's device.
+        The result stays on the device (cloud_get, scene_use_cloud); returns cloud_info()."""
+        dev = _on_device(depth, rgb, intrinsics, poses)
+        if len(depth.shape) != 3:
+            raise ValueError("depth: [F, H, W]")
+        F, H, W = (int(x) for x in depth.shape)
+        if tuple(rgb.shape) != (F, H, W, 3):
+            raise ValueError(f"rgb: shape {(F, H, W, 3)} expected, got {tuple(rgb.shape)} (a colour image of "
+                             "another size than depth is not resized)")
+        keep = [_arg(depth, "float32", (F, H, W), "depth", dev), _arg(rgb, "uint8", (F, H, W, 3), "rgb", dev),
+                _arg(intrinsics, "float64", (F, 4), "intrinsics", dev), _arg(poses, "float64", (F, 4, 4), "poses", dev)]
+        if params is None:
+            params = CloudParams()
+            self.L.mc_cloud_params_default(ctypes.byref(params))
+        if dev:
+            _settle(self)
+        self._check(self.L.mc_cloud_fuse_frames(self.h, F, H, W, keep[0][1], keep[1][1], keep[2][1], keep[3][1],
+                                                1 if dev else 0, ctypes.byref(params)))
+        return self.cloud_info()
+
+    def cloud_voxel_down(self, points, colors=None, voxel_size: float = 0.005):
+        """mc_cloud_voxel_down: one voxel_down_sample of points float64 [n, 3] (colours float64 [n, 3] or
+        None) by the device routine of cloud_fuse; returns cloud_info()."""
+        dev = _on_device(points, colors)
+        n = int(points.shape[0])
+        p = _arg(points, "float64", (n, 3), "points", dev)
+        c = _arg(colors, "float64", (n, 3), "colors", dev) if colors is not None else (None, None)
+        if dev:
+            _settle(self)
+        self._check(self.L.mc_cloud_voxel_down(self.h, n, p[1], c[1], float(voxel_size), 1 if dev else 0))
+        return self.cloud_info()
+
+    def cloud_info(self):
+        """mc_cloud_info: dict of CLOUD_INFO (result points, voxel_down_sample runs, the largest run's input
+        points, the largest voxel population, bytes held)."""
+        out = np.zeros(5, np.int64)
+        self._check(self.L.mc_cloud_info(self.h, _ptr(out)))
+        return dict(zip(CLOUD_INFO, (int(x) for x in out)))
+
+    def cloud_get(self, device: bool = False, colors: bool = True):
+        """mc_cloud_get: (points, colors) float64 [n, 3] of the result as numpy arrays, or with device=True
+        as tensors on the context's device; colors=False (or a result without colours asked so): None."""
+        n = self.cloud_info()["num_points"]
+        if device:
+            import torch
+            _settle(self)
+            pts = torch.empty((n, 3), dtype=torch.float64, device=self.torch_device)
+            col = torch.empty((n, 3), dtype=torch.float64, device=self.torch_device) if colors else None
+            pp = ctypes.c_void_p(pts.data_ptr()) if n else None
+            cp = ctypes.c_void_p(col.data_ptr()) if (colors and n) else None
+            if colors and not n:  # the state check of the colours still runs
+                cp = ctypes.c_void_p(torch.empty(1, dtype=torch.float64, device=self.torch_device).data_ptr())
+        else:
+            pts = np.empty((n, 3), np.float64)
+            col = np.empty((n, 3), np.float64) if colors else None
+            pp, cp = _ptr(pts), _ptr(col)
+        self._check(self.L.mc_cloud_get(self.h, pp, cp, 1 if device else 0))
+        return pts, col
+
+    def scene_use_cloud(self):
+        """mc_scene_use_cloud: the result's points, rounded to float32, become the scene points."""
+        self._check(self.L.mc_scene_use_cloud(self.h))
+
+    for f in (cloud_fuse, cloud_voxel_down, cloud_info, cloud_get, scene_use_cloud):
+        setattr(Context, f.__name__, f)
+
+
+_cloud_methods()
 
 
 def bits_unpack(words, ncols):

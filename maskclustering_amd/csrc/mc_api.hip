@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 #include <thread>
 #include <utility>
@@ -24,6 +25,7 @@
 #include "mc_ap_plan.hpp"
 #include "mc_crop_plan.hpp"
 #include "mc_proj_plan.hpp"
+#include "mc_cloud_plan.hpp"
 #include "mc_kernels.inl"
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
@@ -34,6 +36,7 @@
 #include "mc_ov_kernels.inl"
 #include "mc_crop_kernels.inl"
 #include "mc_proj_kernels.inl"
+#include "mc_cloud_kernels.inl"
 #include "mc_setorder.inl"
 
 using mc::DevBuf;
@@ -271,6 +274,7 @@ int mc_debug_counters(mc_ctx *ctx, int64_t *out, int32_t n, int reset)
 #include "mc_ap_host.inl"
 #include "mc_crop_host.inl"
 #include "mc_proj_host.inl"
+#include "mc_cloud_host.inl"
 
 extern "C" {
 

@@ -133,6 +133,14 @@ struct ProjState {
     std::vector<int32_t> h_gobj, h_goff, h_rframe, h_rout;         // staged until the next call
 };
 
+// scene point cloud fusion (mc_cloud_*; the host code is mc_cloud_host.inl): the result of the last call
+struct CloudState {
+    bool have = false, have_col = false;
+    int64_t n = 0;                                // result points
+    DevBuf pts, col;                              // float64 [n, 3] each
+    int64_t stages = 0, max_in = 0, max_pop = 0;  // voxel_down_sample runs, the largest one's input, the fullest voxel
+};
+
 // scene input (mc_scene_set_masks; the host code is mc_graph_host.inl): the kept masks on the host and the device
 // (P, F and FW are also set by mc_nodes_set, which brings level-0 nodes without a scene)
 struct SceneState {
@@ -254,4 +262,5 @@ struct mc_ctx {
     EvState ev;            // AP evaluation (mc_ev_*)
     CropState crop;        // CLIP crop preparation (mc_crop_*)
     ProjState proj;        // projected boxes (mc_proj_*)
+    CloudState cloud;      // scene point cloud fusion (mc_cloud_*)
 };
