@@ -644,6 +644,52 @@ int mc_cloud_info(mc_ctx *ctx, int64_t *out5);
 int mc_cloud_get(mc_ctx *ctx, double *points, double *colors, int on_device);
 int mc_scene_use_cloud(mc_ctx *ctx);
 
+/* ---- label images from per-frame instance masks -------------------------------------------------------
+ * Replaces the end of step 1 (mask_predict.py:94-113): a 2-D model's instance masks become the uint8
+ * label image S1 reads, ids 1..K by ascending score, at most 255 per frame.  DESIGN.md §2 (f8).
+ *
+ * mc_labels_paint: frames are ragged; frame f owns instances inst_off[f] .. inst_off[f+1]) (host array,
+ * F + 1 entries from 0, non-decreasing; an empty frame yields zeros).  masks [inst_off[F], H, W] of
+ * mask_dtype (MC_PAINT_U8: uint8 or bool bytes, MC_PAINT_F32: float32), scores float32 [inst_off[F]];
+ * on_device applies to both.  Per frame:
+ *   1. instance i is selected iff score[i] >= score_threshold, compared in float32 (a NaN score never is);
+ *   2. selected instances are ordered by ascending score, EQUAL SCORES (-0.0 and +0.0 included) BY
+ *      ASCENDING INSTANCE INDEX (torch's CPU sort gives this order; its CUDA sort does not promise one:
+ *      parity-unpinned on ties);
+ *   3. in that order an instance whose area is < min_pixels is skipped and takes no id; every other one
+ *      is kept, takes the next id from 1 and sets every pixel of its mask to it, later ones overwriting
+ *      earlier ones.  The area is the whole mask's: a kept instance may own no pixel and still takes its id;
+ *   4. a pixel is set iff its value EQUALS 1 (uint8 1, float32 1.0); the area is the number of set
+ *      pixels, which is the reference's torch.sum for 0/1 masks (for other values it differs: a
+ *      documented deviation);
+ *   5. a frame with more than 255 kept instances (numpy raises OverflowError at the 256th) gets status
+ *      MC_PAINT_OVERFLOW, an all-zero image and a label_instance row of -1; the other frames are painted.
+ * labels_out is always a device pointer, uint8 [F, H, W] (it can go to mc_frames_decode with
+ * inputs_on_device or to mc_backproject with on_device).  The four small outputs may each be NULL and
+ * are host arrays or, with out_on_device, device pointers: status [F], num_kept [F] (the kept count,
+ * above 255 on overflow), label_instance [F * 255] (the index within its frame of the instance with id
+ * k + 1; -1 beyond num_kept), instance_area [inst_off[F]] (set pixels of every instance, selected or not).
+ * A call with host inputs or host outputs waits for the stream; one with device inputs and device
+ * outputs does not.
+ *
+ * Scratch (one bit per mask value and, for host inputs, the staged masks) comes from the context and
+ * respects mc_ctx_set_memory_budget (1 GiB when unset): the frames are painted in rounds that fit;
+ * MC_ERR_UNSUPPORTED when one frame alone does not.  Every refusal precedes the first launch and the
+ * first write of context state.  MC_ERR_INVALID: inst_off not non-decreasing from 0, a frame with more
+ * than MC_PAINT_MAX_INSTANCES instances, an unknown mask_dtype, non-positive H or W, H * W > 2^31 - 1,
+ * a negative min_pixels or num_frames, a missing array. */
+typedef struct { float score_threshold; int32_t min_pixels; } mc_paint_params;   /* 0.5f, 400 */
+#define MC_PAINT_OK 0
+#define MC_PAINT_OVERFLOW 1
+#define MC_PAINT_MAX_INSTANCES 1024  /* per frame */
+#define MC_PAINT_U8 0
+#define MC_PAINT_F32 1
+void mc_paint_params_default(mc_paint_params *p);
+int mc_labels_paint(mc_ctx *ctx, int32_t num_frames, int32_t H, int32_t W, const int64_t *inst_off, int32_t mask_dtype,
+                    const void *masks, const float *scores, int on_device, const mc_paint_params *params,
+                    uint8_t *labels_out, int32_t *status, int32_t *num_kept, int32_t *label_instance,
+                    int32_t *instance_area, int out_on_device);
+
 /* host utility: packed little-endian bit rows (bit c of word c/64 = column c) -> one byte per
  * column, rows * ncols bytes (the dense bool point_frame_matrix the reference's callers read,
  * graph/construction.py:40,52), split over host threads.                                      */

@@ -49,6 +49,7 @@ EXPORTED = [
     "mc_proj_boxes", "mc_proj_top_views",
     "mc_cloud_params_default", "mc_cloud_fuse_frames", "mc_cloud_voxel_down", "mc_cloud_info", "mc_cloud_get",
     "mc_scene_use_cloud",
+    "mc_paint_params_default", "mc_labels_paint",
 ]
 MC_COMM_ID_BYTES = 128
 
@@ -125,6 +126,18 @@ class CloudParams(ctypes.Structure):
     """mc_cloud_params: the voxel size (what tasmap2mct_format.py:240 calls depth_trunc=0.005), the depth
     limit (its DEPTH_LIMIT = 20) and the frames of a buffer (buffer_size)."""
     _fields_ = [("voxel_size", ctypes.c_double), ("depth_trunc", ctypes.c_double), ("buffer_frames", ctypes.c_int32)]
+
+
+class PaintParams(ctypes.Structure):
+    """mc_paint_params: the score threshold (mask_predict.py's --confidence-threshold) and the smallest
+    area that is painted (:108)."""
+    _fields_ = [("score_threshold", ctypes.c_float), ("min_pixels", ctypes.c_int32)]
+
+
+MC_PAINT_OK, MC_PAINT_OVERFLOW = 0, 1
+MC_PAINT_MAX_INSTANCES = 1024
+MC_PAINT_MAX_IDS = 255
+MC_PAINT_U8, MC_PAINT_F32 = 0, 1
 
 
 _lib = None
@@ -247,6 +260,9 @@ def load():
         "mc_cloud_info": (ctypes.c_int, [vp, vp]),
         "mc_cloud_get": (ctypes.c_int, [vp, vp, vp, ctypes.c_int]),
         "mc_scene_use_cloud": (ctypes.c_int, [vp]),
+        "mc_paint_params_default": (None, [P(PaintParams)]),
+        "mc_labels_paint": (ctypes.c_int, [vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int, P(PaintParams), vp, vp, vp, vp,
+                                           vp, ctypes.c_int]),
     }
     # MCGRAPH_LIB_PARTIAL=1 (A/B scripts only): an older variant library may lack newer entry points
     partial = os.environ.get("MCGRAPH_LIB_PARTIAL") == "1"
@@ -1412,6 +1428,99 @@ def _cloud_methods():
 
 
 _cloud_methods()
+
+
+def paint_params(**kw) -> PaintParams:
+    """The reference's constants (score_threshold 0.5, min_pixels 400) with optional overrides."""
+    p = PaintParams()
+    load().mc_paint_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"unknown paint parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _paint_methods():
+    def labels_paint(self, masks, scores, inst_off, params: PaintParams | None = None, device: bool = False, shape=None,
+                     mask_dtype=None, labels_out=None):
+        """mc_labels_paint: (labels, status [F], num_kept [F], label_instance [F, 255], instance_area [N]).
+        masks [N, H, W] uint8 / bool / float32 and scores float32 [N]: both numpy arrays, or both tensors
+        on the context's device, or both device pointers (ints; then shape=(H, W) and mask_dtype are
+        required); inst_off: F + 1 offsets into N.  labels is a uint8 [F, H, W] tensor on the context's
+        device (or labels_out, a device pointer or tensor, returned as given).  device=True: the four small
+        outputs are int32 tensors on the device and, with device inputs, nothing waits when the context
+        runs on torch's current stream; otherwise they are numpy arrays."""
+        import torch
+        prm = params or paint_params()
+        off = np.ascontiguousarray(np.asarray(inst_off, np.int64).reshape(-1))
+        if len(off) < 1:
+            raise ValueError("inst_off: F + 1 offsets")
+        F = len(off) - 1
+        ntot = int(off[-1])
+        keep = []
+        if isinstance(masks, int) or isinstance(scores, int):
+            if not (isinstance(masks, int) and isinstance(scores, int)) or shape is None or mask_dtype is None:
+                raise ValueError("device pointers: both masks and scores, with shape=(H, W) and mask_dtype")
+            H, W = (int(x) for x in shape)
+            mp, sp, dev, mdt = ctypes.c_void_p(masks), ctypes.c_void_p(scores), 1, int(mask_dtype)
+        else:
+            masks, scores = (a if hasattr(a, "shape") else np.asarray(a) for a in (masks, scores))
+            on = [hasattr(a, "data_ptr") and a.device.type == "cuda" for a in (masks, scores)]
+            if on[0] != on[1]:
+                raise ValueError("masks and scores: both on the host, or both on the context's device")
+            dev = 1 if on[0] else 0
+            if len(masks.shape) != 3 or int(masks.shape[0]) != ntot or int(scores.shape[0]) != ntot or len(scores.shape) != 1:
+                raise ValueError(f"masks [N, H, W] and scores [N] with N = inst_off[-1] = {ntot}")
+            H, W = int(masks.shape[1]), int(masks.shape[2])
+            if dev:
+                if masks.dtype == torch.bool:
+                    masks = masks.view(torch.uint8)
+                if masks.dtype not in (torch.uint8, torch.float32):
+                    raise ValueError("masks: uint8, bool or float32")
+                mdt = MC_PAINT_F32 if masks.dtype == torch.float32 else MC_PAINT_U8
+                masks, scores = masks.contiguous(), scores.to(torch.float32).contiguous()
+                mp = ctypes.c_void_p(masks.data_ptr()) if ntot else None
+                sp = ctypes.c_void_p(scores.data_ptr()) if ntot else None
+            else:
+                masks, scores = (a.detach().numpy() if hasattr(a, "detach") else a for a in (masks, scores))
+                masks = np.asarray(masks)
+                if masks.dtype == np.bool_:
+                    masks = masks.view(np.uint8)
+                if masks.dtype not in (np.uint8, np.float32):
+                    raise ValueError("masks: uint8, bool or float32")
+                mdt = MC_PAINT_F32 if masks.dtype == np.float32 else MC_PAINT_U8
+                masks, scores = np.ascontiguousarray(masks), np.ascontiguousarray(scores, np.float32)
+                mp, sp = (_ptr(masks), _ptr(scores)) if ntot else (None, None)
+            keep = [masks, scores]
+        if labels_out is None:
+            labels = torch.empty((F, max(H, 0), max(W, 0)), dtype=torch.uint8, device=self.torch_device)
+            lp = ctypes.c_void_p(labels.data_ptr()) if labels.numel() else None
+        else:
+            labels = labels_out
+            lp = ctypes.c_void_p(labels if isinstance(labels, int) else labels.data_ptr())
+        if device:
+            outs = [torch.empty(n, dtype=torch.int32, device=self.torch_device) for n in (F, F, F * MC_PAINT_MAX_IDS, ntot)]
+            ptrs = [ctypes.c_void_p(o.data_ptr()) if o.numel() else None for o in outs]
+        else:
+            outs = [np.zeros(n, np.int32) for n in (F, F, F * MC_PAINT_MAX_IDS, ntot)]
+            ptrs = [_ptr(o) if o.size else None for o in outs]
+        cur = torch.cuda.current_stream(self.torch_device)
+        other = (cur.cuda_stream or 0) != (self.stream() or 0)
+        if other:
+            cur.synchronize()  # the inputs and the fresh outputs live on torch's stream
+        self._check(self.L.mc_labels_paint(self.h, F, H, W, _ptr(off), mdt, mp, sp, dev, ctypes.byref(prm), lp, *ptrs,
+                                           1 if device else 0))
+        if other:
+            self.synchronize()
+        del keep
+        outs[2] = outs[2].reshape(F, MC_PAINT_MAX_IDS)
+        return (labels, *outs)
+
+    Context.labels_paint = labels_paint
+
+
+_paint_methods()
 
 
 def bits_unpack(words, ncols):

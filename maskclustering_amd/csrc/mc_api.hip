@@ -26,6 +26,7 @@
 #include "mc_crop_plan.hpp"
 #include "mc_proj_plan.hpp"
 #include "mc_cloud_plan.hpp"
+#include "mc_paint_plan.hpp"
 #include "mc_kernels.inl"
 #include "mc_bp_kernels.inl"
 #include "mc_pp_kernels.inl"
@@ -37,6 +38,7 @@
 #include "mc_crop_kernels.inl"
 #include "mc_proj_kernels.inl"
 #include "mc_cloud_kernels.inl"
+#include "mc_paint_kernels.inl"
 #include "mc_setorder.inl"
 
 using mc::DevBuf;
@@ -275,6 +277,7 @@ int mc_debug_counters(mc_ctx *ctx, int64_t *out, int32_t n, int reset)
 #include "mc_crop_host.inl"
 #include "mc_proj_host.inl"
 #include "mc_cloud_host.inl"
+#include "mc_paint_host.inl"
 
 extern "C" {
 

@@ -141,6 +141,14 @@ struct CloudState {
     int64_t stages = 0, max_in = 0, max_pop = 0;  // voxel_down_sample runs, the largest one's input, the fullest voxel
 };
 
+// label painter (mc_labels_paint; the host code is mc_paint_host.inl): the context's pools
+struct PaintState {
+    DevBuf planes, stage;                      // a round's bit planes; its masks when they come from the host
+    DevBuf off, scores, area, order;           // instance offsets, scores (host input), areas, kept lists in paint order
+    DevBuf kept, status, labinst;              // per frame: kept count, status; the id -> instance table of a host output
+    std::vector<int64_t> h_off;                // staged until the next call
+};
+
 // scene input (mc_scene_set_masks; the host code is mc_graph_host.inl): the kept masks on the host and the device
 // (P, F and FW are also set by mc_nodes_set, which brings level-0 nodes without a scene)
 struct SceneState {
@@ -263,4 +271,5 @@ struct mc_ctx {
     CropState crop;        // CLIP crop preparation (mc_crop_*)
     ProjState proj;        // projected boxes (mc_proj_*)
     CloudState cloud;      // scene point cloud fusion (mc_cloud_*)
+    PaintState paint;      // label painter (mc_labels_paint)
 };
